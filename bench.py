@@ -7,9 +7,21 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement): value = whole-job samples/s, plus
-`roofline` (dominant kernel family = implicit-GEMM conv on MFMA, timed live with HIP events) and, at
-N=1, `cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded sample).
+Prints ONE JSON line on rank 0: value = whole-job samples/s, ms_per_step = milliseconds of one timed step.  A plain
+run does only what that figure needs: set-up, warm-up, the timed steps, the result line.
+
+    --dump-outputs DIR   after everything else: the model and the optimizer are put back to their seeded initial state
+                         and the timed path (the replayed training step) runs twice more on the last timed batches; what
+                         step 1 returns (loss, loss_dict, logged images), its gradient norm and step 2's loss go to
+                         DIR/step1.*.npy, DIR/step2.loss.npy (float64 / float32).  Step 2's loss is computed
+                         with the weights that step 1's backward, clip and Adam update produced.  The inputs are the same
+                         in every run; the outputs agree up to the rounding of the backward's float atomics.  (The timed
+                         steps' own outputs do not: over tens of training steps that rounding grows far beyond it.)
+    --full               also the measurements beyond the headline figure, after the timed region: `ms_per_step_200`
+                         (200 more replayed steps), `roofline` + `kernels` (dominant kernel family = implicit-GEMM conv
+                         on MFMA, every launch timed live with HIP events in extra eager steps) and, at N=1,
+                         `cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample);
+                         --no-kernel-profile / --no-cpu-baseline drop a part of it
 """
 import argparse
 import json
@@ -64,6 +76,31 @@ def pmc_valu_insts(kind):
 N_SIMD = 256 * 4            # MI355X: 256 CUs x 4 SIMDs; a wave64 vector instruction occupies its SIMD's issue port for 4 cycles
 CLOCK_HZ = 2.4e9            # peak engine clock, /opt/skills/guides/MI355X_MICROARCH.md
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files together
+
+
+def step_outputs(prefix, output):
+    """a training step's return value as host arrays: the loss and every loss_dict entry as float64, the logged images as
+    float32 (copied: the replayed step returns the same static buffers every time)"""
+    torch.cuda.synchronize()
+    arrays = {prefix + "loss": output["loss"].detach().double()}
+    for k, v in sorted(output["loss_dict"].items()):
+        arrays[prefix + "loss_dict." + k.replace("/", "_")] = v.detach().double()
+    for k, v in sorted(output.get("hm", {}).items()):
+        v = v["data"] if isinstance(v, dict) else v
+        arrays[prefix + "hm." + k] = v.detach().float()
+    return {k: v.cpu().numpy() for k, v in arrays.items()}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: DIR/<name>.npy"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "outputs to dump: %d bytes" % total
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
 
 def cpu_baseline(max_seconds=25.0):
     """Oracle (CPU restatement of the reference path, parity-pinned to the reference) on this box's host
@@ -108,8 +145,14 @@ def main():
                          "reference's own size — KITTI-360 fisheye, ResNet-18 + FishEyeDecoder (Mei camera model), 64 depth "
                          "bins, 384x384, batch 16, max depth 150, weight decay 1e-5 (configs/kitti360_fisheye_example:72,"
                          "83-86,198-207), dataset poses")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also ms_per_step_200, the live kernel profile (roofline, kernels) and the "
+                         "CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-kernel-profile", action="store_true", help="--full without the kernel profile")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after everything else, run the timed path for two steps from the seeded initial state and "
+                         "write what they return to DIR/<name>.npy")
     args = ap.parse_args()
     fisheye = args.workload == "fisheye"
     if fisheye:
@@ -153,10 +196,16 @@ def main():
     optimizer = build_optimizer(model, **tc.optimizer)
     hook = build(**tc.training_hook)
     batches = synthetic_device_batches(B, H, W, dev, rank, fisheye=fisheye)
+    # --dump-outputs: the seeded initial state (weights, BatchNorm statistics; the optimizer before its first step), put back
+    # before the dumped steps
+    initial_state = ({k: v.detach().clone() for k, v in model.state_dict().items()} if args.dump_outputs else None)
+    initial_opt = optimizer.state_dict() if args.dump_outputs else None
 
     def run_steps(n, start):
+        out = None
         for i in range(n):
-            hook(dict(batches[(start + i) % len(batches)]), model, optimizer, global_step=start + i)
+            out = hook(dict(batches[(start + i) % len(batches)]), model, optimizer, global_step=start + i)
+        return out
 
     # data parallel: the training hook first times the step with the encoders as two chains and as two lanes on the ranks
     # present and keeps the faster (BaseTrainingHook, encoder-pass autotune) — set-up, before the contract's warm-up steps
@@ -186,7 +235,7 @@ def main():
     # ---- a longer window of the same replayed step, outside the contract's timed region: the driver's default 20 steps are
     # 0.12 s, which does not resolve a per-cent effect ----
     ms_long = None
-    if world == 1 and args.steps < 200 and hook.graph_replays > 0:
+    if args.full and world == 1 and args.steps < 200 and hook.graph_replays > 0:
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         run_steps(200, args_start + args.steps)
@@ -195,7 +244,7 @@ def main():
 
     # ---- live kernel timing for the roofline object (extra steps, outside the timed region) ----
     roofline, extra = None, {}
-    if not args.no_kernel_profile:
+    if args.full and not args.no_kernel_profile:
         # per-launch HIP events need the launches to come from the host: these extra steps run the same kernels
         # eagerly (the timed region above replays them from a hipGraph)
         eager_hook = build(use_graph=False, **tc.training_hook)
@@ -312,6 +361,31 @@ def main():
         conv_time = sum(a[2] for a in allc) / nprof
         extra["conv_time_ms_per_step"] = round(conv_time * 1e3, 3)
 
+    # ---- --dump-outputs (outside the timed region, after everything else): two more steps of the timed path from the seeded
+    # initial state, on the last two timed batches.  The captured step reads the parameters in place and the optimizer
+    # re-adopts a loaded state in place (the resume-from-checkpoint path), so the same graph replays them ----
+    replays = hook.graph_replays            # (the result line's count does not include the dumped steps)
+    if args.dump_outputs:
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            for k, v in model.state_dict().items():
+                v.copy_(initial_state[k])
+        RT.bump_weights()
+        optimizer.load_state_dict(initial_opt)
+        arrays = {}
+        for n in (1, 2):
+            i = args_start + args.steps - 3 + n
+            out = hook(dict(batches[i % len(batches)]), model, optimizer, global_step=i)
+            got = step_outputs("step%d." % n, out)
+            # (step 2: the loss only — its smoothness terms, ~1e-7 each, move by up to 1e-3 of themselves with the rounding
+            # of step 1's update)
+            arrays.update(got if n == 1 else {"step2.loss": got["step2.loss"]})
+            if n == 1 and optimizer.grad_norm() is not None:
+                arrays["step1.grad_norm"] = optimizer.grad_norm().double().cpu().numpy()
+        del out
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
+
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         line = {
@@ -334,7 +408,7 @@ def main():
                                           else "two chains (depth and pose encoder on two streams)")
                                          + ("" if RT.dp is None else "; weight gradients " + RT.dp.wgrad_mode)) if not fisheye else "one network"),
                        "encoder_pass_ms": RT.encoder_pass_ms, "autotune_steps": pre,
-                       "hipgraph_replays": hook.graph_replays, "frames_per_s": round(3 * B * world * args.steps / elapsed, 1),
+                       "hipgraph_replays": replays, "frames_per_s": round(3 * B * world * args.steps / elapsed, 1),
                        "dp_collectives": (None if RT.dp is None else ("rccl-direct" + ("+hipgraph" if RT.dp.capturable else "")
                                                                         if RT.dp.direct else "torch.distributed")),
                        "dp_world": (None if RT.dp is None else RT.dp.world),
@@ -343,7 +417,7 @@ def main():
                        "gradient_buckets_per_step": (None if RT.dp is None else RT.dp.n_bucket)},
             "roofline": roofline, "kernels": extra,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line))
     if world > 1:

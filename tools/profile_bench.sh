@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp PYTHONPATH=$R
-rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench --output-format csv -- python $R/bench.py --steps 50 --warmup 10 --no-cpu-baseline $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench --output-format csv -- python $R/bench.py --steps 50 --warmup 10 --full --no-cpu-baseline $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err
 python - <<PY
 import csv, glob, subprocess
 rows = []
@@ -15,7 +15,7 @@ for f in glob.glob("$OUT/trace/**/*kernel_stats.csv", recursive=True):
     rows = list(csv.DictReader(open(f)))
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
 with open("$OUT/kernel_stats.md", "w") as o:
-    o.write("rocprofv3 --kernel-trace --stats -- python bench.py --steps 50 --warmup 10 --no-cpu-baseline $BENCH_ARGS\n")
+    o.write("rocprofv3 --kernel-trace --stats -- python bench.py --steps 50 --warmup 10 --full --no-cpu-baseline $BENCH_ARGS\n")
     o.write("(60 replayed steps + 3 eager profiling steps + warm-up/capture; durations in the profiled run)\n\n")
     o.write("| kernel | calls | total ms | avg us | % |\n|---|---|---|---|---|\n")
     for r in sorted(rows, key=lambda r: -float(r["TotalDurationNs"])):
