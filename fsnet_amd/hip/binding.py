@@ -155,7 +155,20 @@ class FsSmoothArgs(C.Structure):
     ]
 
 
-ABI_VERSION = 11     # FS_ABI_VERSION of include/fsnet_hip.h (tests/test_abi.py holds the two together)
+class FsPostOptArgs(C.Structure):
+    _fields_ = [
+        ("image", C.c_void_p), ("depth", C.c_void_p), ("vo", C.c_void_p), ("centres", C.c_void_p),
+        ("out", C.c_void_p), ("labels", C.c_void_p), ("nseg", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+        ("rgb_mean", C.c_double * 3), ("rgb_std", C.c_double * 3),
+        ("lab_dist_weight", C.c_float), ("depth_dist_weight", C.c_float), ("image_dist_weight", C.c_float),
+        ("lambda0", C.c_double), ("lambda1", C.c_double), ("lambda2", C.c_double),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("iter_num", C.c_int32),
+        ("max_points", C.c_int32),
+    ]
+
+
+ABI_VERSION = 12     # FS_ABI_VERSION of include/fsnet_hip.h (tests/test_abi.py holds the two together)
 _lib = None
 
 

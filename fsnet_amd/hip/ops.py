@@ -5,7 +5,7 @@ import os
 
 import torch
 
-from .binding import (lib, check, stream_ptr, FsBnApplyArgs, FsBnBwdArgs, FsPhotoArgs, FsSmoothArgs)
+from .binding import (lib, check, stream_ptr, FsBnApplyArgs, FsBnBwdArgs, FsPhotoArgs, FsPostOptArgs, FsSmoothArgs)
 from .conv import dtype_code, _timed, BN_EPS, BN_MOMENTUM, Spec, run_specs
 
 STAT_SLOTS = 8   # FS_STAT_SLOTS in include/fsnet_hip.h
@@ -737,7 +737,7 @@ def counter_incr(buf):
 
 
 # ---------------------------------------------------------------------------------------------
-# evaluation
+# evaluation and the sparse-VO post-optimisation
 # ---------------------------------------------------------------------------------------------
 def resize_linear(src, H, W, invert=False):
     """src: device fp32 [h, w] -> [H, W] with OpenCV's INTER_LINEAR rule (invert: 1 / resize(1 / src))."""
@@ -759,6 +759,61 @@ def depth_eval(pred, gt):
     scratch = torch.empty(gt.numel() * 2, dtype=torch.float32, device=pred.device)
     check(lib.fs_depth_eval(pred.data_ptr(), gt.data_ptr(), pred.shape[0], pred.shape[1], pred.shape[2], gt.shape[1],
                             gt.shape[2], scratch.data_ptr(), out.data_ptr(), stream_ptr()), "depth_eval")
+    return out
+
+
+_CENTRE_TABLES = {}
+
+
+def postopt_centres(h_seg, w_seg, device):
+    """the SLIC start table [K, 2] fp32 on `device` (postopt_utils.py:108-112): numpy's meshgrid of
+    arange(-1, 1, 2/h_seg) x arange(-1, 1, 2/w_seg), K from numpy's arange.  Cached, so a captured call copies
+    nothing from the host."""
+    import numpy as np
+    key = (float(h_seg), float(w_seg), str(device))
+    t = _CENTRE_TABLES.get(key)
+    if t is None:
+        c = np.stack(np.meshgrid(np.arange(-1, 1.0, 2.0 / h_seg), np.arange(-1, 1.0, 2.0 / w_seg), indexing='ij'),
+                     axis=-1).reshape(-1, 2)
+        t = torch.from_numpy(np.ascontiguousarray(c.astype(np.float32))).to(device)
+        _CENTRE_TABLES[key] = t
+    return t
+
+
+def post_optimize(image, depth, vo, *, h_seg, w_seg, iter_num, lab_dist_weight, depth_dist_weight, image_dist_weight,
+                  lambda0, lambda1, lambda2, max_points=800, rgb_mean, rgb_std, return_labels=False):
+    """Sparse-VO depth post-optimisation of B images in one fs_postopt call (postopt_utils.py:170-226).
+    image [B,3,H,W] normalised, depth [B,H,W] (> 0), vo [B,H,W] (metres): device fp32.  Returns the refined depth
+    [B,H,W]; with return_labels also the int32 segment labels [B,H,W] (compacted to the non-empty segments, index
+    order) and the int32 count of non-empty segments [B]."""
+    assert image.is_cuda and image.dim() == 4 and image.shape[1] == 3
+    B, _, H, W = image.shape
+    assert depth.shape == (B, H, W) and vo.shape == (B, H, W)
+    image = image.float().contiguous()
+    depth = depth.float().contiguous()
+    vo = vo.float().contiguous()
+    ctab = postopt_centres(h_seg, w_seg, image.device)
+    K = ctab.shape[0]
+    nbytes = int(lib.fs_postopt_workspace_bytes(B, H, W, K))
+    if nbytes < 0:
+        raise ValueError("post_optimize: %d segment slots / %dx%d images are outside the kernel's limits" % (K, H, W))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=image.device)
+    out = torch.empty_like(depth)
+    labels = torch.empty(B, H, W, dtype=torch.int32, device=image.device) if return_labels else None
+    nseg = torch.empty(B, dtype=torch.int32, device=image.device) if return_labels else None
+    a = FsPostOptArgs()
+    a.image, a.depth, a.vo, a.centres, a.out = image.data_ptr(), depth.data_ptr(), vo.data_ptr(), ctab.data_ptr(), \
+        out.data_ptr()
+    a.labels, a.nseg = _p(labels), _p(nseg)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    for i in range(3):
+        a.rgb_mean[i], a.rgb_std[i] = float(rgb_mean[i]), float(rgb_std[i])
+    a.lab_dist_weight, a.depth_dist_weight, a.image_dist_weight = lab_dist_weight, depth_dist_weight, image_dist_weight
+    a.lambda0, a.lambda1, a.lambda2 = lambda0, lambda1, lambda2
+    a.B, a.H, a.W, a.K, a.iter_num, a.max_points = B, H, W, K, int(iter_num), int(max_points)
+    check(lib.fs_postopt(C.byref(a), stream_ptr()), "postopt")
+    if return_labels:
+        return out, labels, nseg
     return out
 
 

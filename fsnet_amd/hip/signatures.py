@@ -41,6 +41,8 @@ SIGNATURES = {
     "fs_distill_bwd": (C.c_int, [P, P, P, L, P, P, P, P]),
     "fs_resize_linear": (C.c_int, [P, P, I, I, I, I, I, P]),
     "fs_depth_eval": (C.c_int, [P, P, I, I, I, I, I, P, P, P]),
+    "fs_postopt": (C.c_int, [P, P]),
+    "fs_postopt_workspace_bytes": (C.c_int64, [I, I, I, I]),
     "fs_copy_multi": (C.c_int, [P, P, P, I, P]),
     "fs_zero_multi": (C.c_int, [P, P, I, P]),
     "fs_pack_tile_blocks": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -25,3 +25,12 @@ def cam_relative_pose(T_imu2world_0, T_imu2world_1, T_imu2vel, T_vel2cam):
     """pose of camera frame 0 expressed in camera frame 1 (reference :53-54)"""
     return T_vel2cam @ T_imu2vel @ np.linalg.inv(T_imu2world_1) @ T_imu2world_0 @ np.linalg.inv(T_imu2vel) \
         @ np.linalg.inv(T_vel2cam)
+
+
+def read_vo_depth(path):
+    """sparse visual-odometry depth, 16-bit PNG -> float64 metres: / 65535 * 120, values < 3 or > 80 set to 120 (the
+    reference's marker for "no point"; postopt_utils.py:50-53 reads it with cv2.imread(path, -1))"""
+    d = np.asarray(Image.open(path, 'r'), dtype=np.float64) / 65535.0 * 120
+    d[d < 3] = 120
+    d[d > 80] = 120
+    return d

@@ -2,13 +2,14 @@
 (monodepth/pipeline_hooks/evaluation_hooks/base_evaluation_hooks.py:19-67): eval-mode forward over the validation set,
 crop to the effective size, inverse-depth resize to the original image size, per-image errors, mean + log.
 Everything between the network output and the 15 numbers per image stays on the device (fs_resize_linear with
-invert, fs_depth_eval); only those numbers are copied back.  The post-optimisation variant (:69-127, sparse visual
-odometry) is out of scope."""
+invert, fs_depth_eval); only those numbers are copied back.  KittiEvaluationHook_postopt (:69-127) refines the
+prediction with sparse visual-odometry depth first (ops.post_optimize, one call per batch on the device)."""
 import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
 from fsnet_amd.hip import ops
+from fsnet_amd.monodepth.networks.utils import postopt_utils as PU
 from fsnet_amd.vision_base.data.datasets.dataset_utils import collate_fn
 from fsnet_amd.vision_base.utils.builder import build
 
@@ -47,3 +48,92 @@ class KittiEvaluationHook(object):
         self.dataset_eval_func.log(writer, mean_errors, mean_abs_errors, global_step=global_step, epoch_num=epoch_num)
         meta_arch.train()
         return dict(mean_errors=mean_errors, mean_abs_errors=mean_abs_errors, ratios=res[:, 0])
+
+
+class KittiEvaluationHook_postopt(KittiEvaluationHook):
+    """KittiEvaluationHook with the sparse-VO post-optimisation in front of the metrics (reference :69-127):
+    post_opt_cfg (dict or EasyDict) overrides lab_dist_weight, depth_dist_weight, image_dist_weight, h_seg, w_seg,
+    iter_num, lambda0, lambda1, lambda2 (hook defaults 1, 1, 1, 10, 18, 3, 0.54/180, 1, 0.4) and, as an addition,
+    max_points (800); vo_path is the folder of the VO depth PNGs (read_sparse_vo).  Each batch is refined in one
+    ops.post_optimize call, then evaluated like KittiEvaluationHook.
+
+    Deliberate deviations from the reference:
+      - the image is cropped to the effective size together with the depth (the reference pairs the full-size image
+        with the cropped depth, which fails whenever the two differ, and its bare except hides the failure);
+      - sample i uses its own image (the reference uses image[0] for every sample; the same at batch_size 1);
+      - a batch that carries ('vo_depth', 0) is refined with it (the reference reads it and then skips refinement);
+        it must have the effective size, else ValueError;
+      - no bare except: a frame whose VO file is missing is evaluated unrefined and counted in n_unrefined; any other
+        error propagates."""
+    PARAM_DEFAULTS = dict(lab_dist_weight=1, depth_dist_weight=1, image_dist_weight=1, h_seg=10, w_seg=18, iter_num=3,
+                          lambda0=0.54 / (10 * 18), lambda1=1.0, lambda2=0.4, max_points=800)
+
+    def _post_opt_params(self):
+        cfg = getattr(self, 'post_opt_cfg', None) or dict()
+        params = dict(self.PARAM_DEFAULTS)
+        for key in params:
+            if key in cfg:
+                params[key] = cfg[key]
+        return params, cfg.get('vo_path', None)
+
+    def _vo_of(self, batched_data, dataset_val, i, frame_index, h, w, vo_path, device):
+        if ('vo_depth', 0) in batched_data:
+            vo = batched_data[('vo_depth', 0)][i]
+            vo = vo if isinstance(vo, torch.Tensor) else torch.as_tensor(np.asarray(vo))
+            if tuple(vo.shape) != (h, w):
+                raise ValueError("('vo_depth', 0) of sample %d is %s, the effective size is %s" % (
+                    i, tuple(vo.shape), (h, w)))
+        else:
+            try:
+                vo = torch.from_numpy(PU.read_sparse_vo(dataset_val, frame_index, h, w, vo_folder=vo_path))
+            except FileNotFoundError:
+                return None
+        return vo.to(device, torch.float32)
+
+    @torch.no_grad()
+    def __call__(self, meta_arch, dataset_val, writer=None, global_step=0, epoch_num=0):
+        meta_arch.eval()
+        params, vo_path = self._post_opt_params()
+        batch_size = getattr(self, 'batch_size', 1)
+        num_workers = getattr(self, 'num_workers', 4)
+        dataloader = DataLoader(dataset_val, batch_size, shuffle=False, num_workers=num_workers, collate_fn=collate_fn)
+        rows = []
+        frame_index = 0
+        n_refined = n_unrefined = 0
+        for batched_data in dataloader:
+            output_dict = self.test_hook(batched_data, meta_arch, global_step, epoch_num)
+            depth_b = output_dict['depth']
+            image_b = batched_data[('image', 0)]
+            B = depth_b.shape[0]
+            crops, groups = [], {}
+            for i in range(B):
+                h_eff, w_eff = (int(v) for v in batched_data[('image_resize', 'effective_size')][i])
+                depth = depth_b[i, 0, 0:h_eff, 0:w_eff].float()
+                vo = self._vo_of(batched_data, dataset_val, i, frame_index + i, h_eff, w_eff, vo_path, depth.device)
+                crops.append(depth.contiguous())
+                if vo is None:
+                    n_unrefined += 1
+                    continue
+                image = torch.as_tensor(image_b[i])[:, 0:h_eff, 0:w_eff].to(depth.device, torch.float32)
+                groups.setdefault((h_eff, w_eff), []).append((i, image, depth, vo))
+            for items in groups.values():       # one call per batch (per effective size, which a batch shares)
+                refined = ops.post_optimize(torch.stack([t[1] for t in items]), torch.stack([t[2] for t in items]),
+                                            torch.stack([t[3] for t in items]), rgb_mean=PU.IMAGENET_MEAN,
+                                            rgb_std=PU.IMAGENET_STD, **params)
+                for j, t in enumerate(items):
+                    crops[t[0]] = refined[j]
+                n_refined += len(items)
+            for i in range(B):
+                h, w = (int(v) for v in batched_data[('original_image', 0)][i].shape[:2])
+                depth_0 = ops.resize_linear(crops[i], h, w, invert=True)          # 1 / cv2.resize(1 / depth, (w, h))
+                gt = self.dataset_eval_func._gt(frame_index, depth_0.device)
+                rows.append(ops.depth_eval(depth_0[None], gt[None])[0])
+                frame_index += 1
+        res = torch.stack(rows).cpu().numpy()
+        if (res[:, 15] == 0).any():
+            raise ValueError
+        mean_errors, mean_abs_errors = res[:, 1:8].mean(0), res[:, 8:15].mean(0)
+        self.dataset_eval_func.log(writer, mean_errors, mean_abs_errors, global_step=global_step, epoch_num=epoch_num)
+        meta_arch.train()
+        return dict(mean_errors=mean_errors, mean_abs_errors=mean_abs_errors, ratios=res[:, 0],
+                    errors=res[:, 1:8], abs_errors=res[:, 8:15], n_refined=n_refined, n_unrefined=n_unrefined)

@@ -33,7 +33,7 @@ extern "C" {
 
 /* library/ABI version and the ISA the kernels were compiled for ("gfx950").  FS_ABI_VERSION changes whenever an
  * argument struct or a signature below does; a host binding refuses a library that reports another number. */
-#define FS_ABI_VERSION 11
+#define FS_ABI_VERSION 12
 int fs_abi_version(void);
 const char* fs_target_arch(void);
 /* debugging aid: writes the device's constant-rate clock (wall_clock64, 100 MHz) into *slot (u64) on `stream`;
@@ -343,6 +343,36 @@ int fs_resize_frames(const FsResizeArgs* args, void* stream);
 int fs_resize_linear(const float* src, float* dst, int h, int w, int H, int W, int invert, void* stream);
 int fs_depth_eval(const float* pred, const float* gt, int B, int h, int w, int H, int W, void* scratch,
                   double* out16, void* stream);
+
+/* Sparse-VO depth post-optimisation (postopt_utils.py:8-11, 94-226; KittiEvaluationHook_postopt,
+ * base_evaluation_hooks.py:69-127), B images in one fixed launch sequence (capturable: no host sync, the launch count
+ * depends on iter_num alone).  Per image: denorm (f64, truncating uint8 cast) -> rgb2lab -> SLIC over (Lab, x, y, depth)
+ * from the K grid_sample centres of `centres` ([K][2] fp32, component 0 read as x) for iter_num iterations with the
+ * reference's early stop -> VO mask (3 < vo < 80, and the max_points smallest |log d - log vo| over all pixels when
+ * at least max_points are valid; ties at the threshold lowest pixel index first) -> per-segment log-scale targets ->
+ * A x = rhs (A = diag(l0 s + l1 m + l2) - l0 W over the non-empty segments, fp64 CG) -> out = exp(log d + x - base).
+ * image [B][3][H][W] normalised, depth / vo / out [B][H][W]; labels [B][H][W] (segment index compacted to the non-empty
+ * segments, index order) and nseg [B] (non-empty segments) are optional.  Deterministic: exact fixed-point sums.
+ * FS_EINVAL: K outside 1..1024, H*W >= 2^31, iter_num < 1, max_points < 1, lambda2 <= 0, lambda0 or lambda1 < 0,
+ * workspace_bytes < fs_postopt_workspace_bytes(B, H, W, K) (which is -1 for shapes outside those limits). */
+typedef struct FsPostOptArgs {
+  const float* image;
+  const float* depth;
+  const float* vo;
+  const float* centres;
+  float* out;
+  int32_t* labels;
+  int32_t* nseg;
+  void* workspace;
+  int64_t workspace_bytes;
+  double rgb_mean[3];
+  double rgb_std[3];
+  float lab_dist_weight, depth_dist_weight, image_dist_weight;
+  double lambda0, lambda1, lambda2;
+  int32_t B, H, W, K, iter_num, max_points;
+} FsPostOptArgs;
+int fs_postopt(const FsPostOptArgs* args, void* stream);
+int64_t fs_postopt_workspace_bytes(int B, int H, int W, int K);
 
 /* n <= FS_COPY_MAX device-to-device copies (16-byte aligned pointers, any byte counts) in one launch: the training
  * hook stages a batch into the static input buffers of its captured hipGraph with it

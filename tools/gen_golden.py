@@ -994,7 +994,58 @@ def gen_onnx():
         len(g["nodes"]), len(g["initializers"]), float(pred["depth"].min()), float(pred["depth"].max())))
 
 
+def gen_postopt():
+    """sparse-VO depth post-optimisation through the REAL reference post_optimization (postopt_utils.py:170-226) on
+    CPU, with the skimage shim's rgb2lab; its own SLIC is wrapped to record labels (compacted to the non-empty
+    segments, in index order) and centres.  The reference leaves the order of top-k ties open, so the VO points carry
+    noise (distinct |log pred - log vo|).  (a) 96x320 at the hook defaults with > max_points valid VO points (the
+    top-k branch); (b) 64x200 at the function defaults with fewer."""
+    import time
+    from monodepth.networks.utils import postopt_utils as PU
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import helpers_postopt as HP
+    rec = {}
+    slic0 = PU.SLIC
+
+    def slic_rec(*a, **k):
+        centers, segments = slic0(*a, **k)
+        H, W = a[0].shape[:2]
+        lab = np.full((H, W), -1, np.int16)
+        for i, s in enumerate(segments):
+            lab[s[:, 0].numpy(), s[:, 1].numpy()] = i
+        rec["labels"], rec["centres"] = lab, npy(centers).T.astype(np.float32)
+        return centers, segments
+    PU.SLIC = slic_rec
+    out = {}
+    cases = {"a": (96, 320, 21, 0.03, dict(HP.HOOK_DEFAULTS), 800),
+             "b": (64, 200, 22, 0.02, dict(HP.FUNCTION_DEFAULTS, h_seg=6, w_seg=10), 800)}
+    for tag, (H, W, seed, frac, params, max_points) in cases.items():
+        image, _, pred, vo = HP.synthetic_scene(H, W, seed, vo_frac=frac, vo_noise=0.05)   # no top-k ties
+        rgb = PU.denorm(image.transpose(1, 2, 0), rgb_mean=np.array([0.485, 0.456, 0.406]),
+                        rgb_std=np.array([0.229, 0.224, 0.225]))
+        t0 = time.time()
+        ref = PU.post_optimization(rgb, PU.depth_image_to_point_cloud_array(pred), torch.from_numpy(pred), vo,
+                                   max_points=max_points, **params)
+        n_valid = int(((vo > 3) & (vo < 80)).sum())
+        print("postopt %s: %dx%d, %d valid VO points, %d segments, %.1f s" % (
+            tag, H, W, n_valid, rec["centres"].shape[0], time.time() - t0))
+        mine, seg, centres, _, _ = HP.post_optimize(image, pred, vo, max_points=max_points, details=True, **params)
+        print("  restatement: labels equal on %.5f, max rel depth dev %.3e" % (
+            float((seg.numpy() == rec["labels"]).mean()), float((mine / ref - 1).abs().max())))
+        out.update({"%s_image" % tag: image, "%s_depth" % tag: pred, "%s_vo" % tag: vo,
+                    "%s_labels" % tag: rec["labels"], "%s_centres" % tag: rec["centres"],
+                    "%s_refined" % tag: npy(ref).astype(np.float32),
+                    "%s_params" % tag: np.array([H, W, params["h_seg"], params["w_seg"], params["iter_num"],
+                                                 params["lambda0"], params["lambda1"], params["lambda2"],
+                                                 max_points], np.float64)})
+    PU.SLIC = slic0
+    np.savez_compressed(os.path.join(GOLD, "postopt.npz"), **out)
+
+
 if __name__ == "__main__":
+    if "--only-postopt" in sys.argv:
+        gen_postopt()
+        sys.exit(0)
     if "--only-onnx" in sys.argv:
         gen_onnx()
         sys.exit(0)
@@ -1052,5 +1103,6 @@ if __name__ == "__main__":
     gen_augment_resize()
     gen_no_overlap_mask()
     gen_velo_gt()
+    gen_postopt()
     for f in sorted(os.listdir(GOLD)):
         print(f, os.path.getsize(os.path.join(GOLD, f)) // 1024, "KiB")
