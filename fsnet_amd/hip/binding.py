@@ -168,7 +168,25 @@ class FsPostOptArgs(C.Structure):
     ]
 
 
-ABI_VERSION = 12     # FS_ABI_VERSION of include/fsnet_hip.h (tests/test_abi.py holds the two together)
+class FsFlowArgs(C.Structure):
+    _fields_ = [
+        ("img0", C.c_void_p), ("img1", C.c_void_p), ("flow", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+        ("pyr_scale", C.c_double), ("poly_sigma", C.c_double),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("levels", C.c_int32), ("winsize", C.c_int32),
+        ("iterations", C.c_int32), ("poly_n", C.c_int32), ("flags", C.c_int32),
+    ]
+
+
+class FsMotionMaskArgs(C.Structure):
+    _fields_ = [
+        ("flow", C.c_void_p), ("P2", C.c_void_p), ("pose", C.c_void_p), ("mask", C.c_void_p),
+        ("threshold", C.c_float), ("mode", C.c_int32),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+    ]
+
+
+ABI_VERSION = 13     # FS_ABI_VERSION of include/fsnet_hip.h (tests/test_abi.py holds the two together)
 _lib = None
 
 

@@ -5,7 +5,8 @@ import os
 
 import torch
 
-from .binding import (lib, check, stream_ptr, FsBnApplyArgs, FsBnBwdArgs, FsPhotoArgs, FsPostOptArgs, FsSmoothArgs)
+from .binding import (lib, check, stream_ptr, FsBnApplyArgs, FsBnBwdArgs, FsFlowArgs, FsMotionMaskArgs, FsPhotoArgs,
+                      FsPostOptArgs, FsSmoothArgs)
 from .conv import dtype_code, _timed, BN_EPS, BN_MOMENTUM, Spec, run_specs
 
 STAT_SLOTS = 8   # FS_STAT_SLOTS in include/fsnet_hip.h
@@ -814,6 +815,114 @@ def post_optimize(image, depth, vo, *, h_seg, w_seg, iter_num, lab_dist_weight, 
     check(lib.fs_postopt(C.byref(a), stream_ptr()), "postopt")
     if return_labels:
         return out, labels, nseg
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# motion masks: dense Farneback flow and the epipolar mask (base_precompute_hooks.py:27-148), and ground-truth masks
+# through the augmentation plan
+# ---------------------------------------------------------------------------------------------
+OPTFLOW_FARNEBACK_GAUSSIAN = 256
+
+
+def _flow_args(B, H, W, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags):
+    """FsFlowArgs of the parameters, each checked here so that a bad one names itself (the C ABI says FS_EINVAL)"""
+    if not 0.0 < float(pyr_scale) < 1.0:
+        raise ValueError("optical_flow_farneback: pyr_scale must lie in (0, 1), got %r" % (pyr_scale,))
+    if not 0 <= int(levels) <= 15:
+        raise ValueError("optical_flow_farneback: levels must lie in 0..15, got %r" % (levels,))
+    if not 1 <= int(winsize) <= 129:
+        raise ValueError("optical_flow_farneback: winsize must lie in 1..129, got %r" % (winsize,))
+    if int(iterations) < 1:
+        raise ValueError("optical_flow_farneback: iterations must be >= 1, got %r" % (iterations,))
+    if int(poly_n) not in (5, 7):
+        raise ValueError("optical_flow_farneback: poly_n must be 5 or 7, got %r" % (poly_n,))
+    if not float(poly_sigma) >= 0.0:
+        raise ValueError("optical_flow_farneback: poly_sigma must be >= 0, got %r" % (poly_sigma,))
+    if int(flags) not in (0, OPTFLOW_FARNEBACK_GAUSSIAN):
+        raise ValueError("optical_flow_farneback: flags must be 0 or OPTFLOW_FARNEBACK_GAUSSIAN (256), got %r"
+                         % (flags,))
+    a = FsFlowArgs()
+    a.pyr_scale, a.poly_sigma = float(pyr_scale), float(poly_sigma)
+    a.B, a.H, a.W, a.levels, a.winsize = B, H, W, int(levels), int(winsize)
+    a.iterations, a.poly_n, a.flags = int(iterations), int(poly_n), int(flags)
+    return a
+
+
+def optical_flow_farneback(img0, img1, pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5, poly_sigma=1.2,
+                           flags=0, workspace=None, out=None):
+    """cv2.calcOpticalFlowFarneback(gray(img0), gray(img1), None, ...) of B frame pairs in one fs_optflow_farneback
+    call.  img0 / img1: device uint8 [B,H,W,3] (gray as cv2 COLOR_BGR2GRAY, channel 0 weighted as blue).  Returns
+    flow [B,H,W,2] fp32 (x, y).  workspace / out: optional preallocated uint8 / fp32 tensors (a captured graph keeps
+    its own)."""
+    assert img0.is_cuda and img0.dtype == torch.uint8 and img0.dim() == 4 and img0.shape[-1] == 3
+    assert img1.shape == img0.shape and img1.dtype == torch.uint8
+    B, H, W, _ = img0.shape
+    img0, img1 = img0.contiguous(), img1.contiguous()
+    a = _flow_args(B, H, W, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags)
+    nbytes = int(lib.fs_optflow_workspace_bytes(C.byref(a)))
+    if nbytes < 0:
+        raise ValueError("optical_flow_farneback: %dx%d frames are outside the kernel's limits" % (H, W))
+    ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=img0.device)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes
+    flow = out if out is not None else torch.empty(B, H, W, 2, dtype=torch.float32, device=img0.device)
+    assert flow.shape == (B, H, W, 2) and flow.dtype == torch.float32 and flow.is_contiguous()
+    a.img0, a.img1, a.flow, a.workspace, a.workspace_bytes = img0.data_ptr(), img1.data_ptr(), flow.data_ptr(), \
+        ws.data_ptr(), nbytes
+    check(lib.fs_optflow_farneback(C.byref(a), stream_ptr()), "optflow_farneback")
+    return flow
+
+
+def optflow_level_image(img0, img1, level, h, w, pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5,
+                        poly_sigma=1.2, flags=0):
+    """pyramid level `level` (h x w) of the gray pair as optical_flow_farneback builds it -> fp32 [B,2,h,w]"""
+    B, H, W, _ = img0.shape
+    img0, img1 = img0.contiguous(), img1.contiguous()
+    a = _flow_args(B, H, W, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags)
+    nbytes = int(lib.fs_optflow_workspace_bytes(C.byref(a)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=img0.device)
+    out = torch.empty(B, 2, h, w, dtype=torch.float32, device=img0.device)
+    a.img0, a.img1, a.workspace, a.workspace_bytes = img0.data_ptr(), img1.data_ptr(), ws.data_ptr(), nbytes
+    check(lib.fs_optflow_level_image(C.byref(a), int(level), out.data_ptr(), stream_ptr()), "optflow_level_image")
+    return out
+
+
+def optflow_workspace_bytes(B, H, W, pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5, poly_sigma=1.2,
+                            flags=0):
+    return int(lib.fs_optflow_workspace_bytes(C.byref(
+        _flow_args(B, H, W, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags))))
+
+
+def motion_mask(flow, P2, rel_pose, threshold=5.0, mode=0):
+    """epipolar motion mask of B flows (base_precompute_hooks.py:58-89 for mode 0, :109-148 for mode 1).
+    flow: device fp32 [B,H,W,2]; P2 [B,3,4] and rel_pose [B,4,4] (any float dtype, any device; used in f64).
+    Returns uint8 [B,H,W] of 0 / 1."""
+    if int(mode) not in (0, 1):
+        raise ValueError("motion_mask: mode must be 0 (|d| > thr) or 1 (|d| / |flow| > thr), got %r" % (mode,))
+    assert flow.is_cuda and flow.dim() == 4 and flow.shape[-1] == 2
+    B, H, W, _ = flow.shape
+    flow = flow.float().contiguous()
+    P2 = torch.as_tensor(P2).to(flow.device, torch.float64).reshape(B, 3, 4).contiguous()
+    pose = torch.as_tensor(rel_pose).to(flow.device, torch.float64).reshape(B, 4, 4).contiguous()
+    mask = torch.empty(B, H, W, dtype=torch.uint8, device=flow.device)
+    a = FsMotionMaskArgs()
+    a.flow, a.P2, a.pose, a.mask = flow.data_ptr(), P2.data_ptr(), pose.data_ptr(), mask.data_ptr()
+    a.threshold, a.mode, a.B, a.H, a.W = float(threshold), int(mode), B, H, W
+    check(lib.fs_motion_mask(C.byref(a), stream_ptr()), "motion_mask")
+    return mask
+
+
+def augment_masks(src, H, W, minv=None, dims=None, iplan=None):
+    """uint8 ground-truth masks [B,Hs,Ws] (device) through the augmentation plan of fs_augment_frames (minv [B,6] f64 +
+    iplan [B,8] int32) or fs_resize_frames (dims [B,4] int32, iplan optional) -> fp32 [B,H,W]"""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.dim() == 3
+    if (minv is None) == (dims is None):
+        raise ValueError("augment_masks: exactly one of minv (warp) and dims (resize) is needed")
+    B, Hs, Ws = src.shape
+    src = src.contiguous()
+    out = torch.empty(B, H, W, dtype=torch.float32, device=src.device)
+    check(lib.fs_augment_masks(src.data_ptr(), _p(minv), _p(dims), _p(iplan), out.data_ptr(), B, Hs, Ws, H, W,
+                               stream_ptr()), "augment_masks")
     return out
 
 

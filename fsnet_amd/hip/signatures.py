@@ -43,6 +43,11 @@ SIGNATURES = {
     "fs_depth_eval": (C.c_int, [P, P, I, I, I, I, I, P, P, P]),
     "fs_postopt": (C.c_int, [P, P]),
     "fs_postopt_workspace_bytes": (C.c_int64, [I, I, I, I]),
+    "fs_optflow_farneback": (C.c_int, [P, P]),
+    "fs_optflow_workspace_bytes": (C.c_int64, [P]),
+    "fs_optflow_level_image": (C.c_int, [P, I, P, P]),
+    "fs_motion_mask": (C.c_int, [P, P]),
+    "fs_augment_masks": (C.c_int, [P, P, P, P, P, I, I, I, I, I, P]),
     "fs_copy_multi": (C.c_int, [P, P, P, I, P]),
     "fs_zero_multi": (C.c_int, [P, P, I, P]),
     "fs_pack_tile_blocks": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),

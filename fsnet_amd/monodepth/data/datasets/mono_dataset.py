@@ -5,14 +5,20 @@
 augmentation.  With the mirrored augmentation classes the frames stay uint8 and the pixel work runs on the device
 (vision_base/data/augmentations: DeviceAugment); the dataset itself only decodes PNGs and does 4x4 algebra.
 
-Not mirrored: precomputed motion masks / optical flow (cv2.imread of side products no shipped config enables)."""
+Precomputed side products (reference :144-149, 194-198, 241-250): with is_motion_mask the sample carries
+'motion_mask', uint8 [H, W] read with PIL from `motion_mask_path/{i:08d}.png` (written by MotionMaskPrecomputeHook);
+with is_precompute_flow it carries 'flow', fp32 [H, W, 2] from the 16-bit 3-channel PNG `flow_path/{i:08d}.png`
+(channels (2, 1) of the file, i.e. cv2's BGR 0:2, then (v - 2^15) / 64).  i is the dataset's own index after the
+static filter, as in the reference; the hook writes the index of the dataset it was given, so inside a ConcatDataset
+of several children the two would disagree, and ConcatDataset refuses that combination."""
 import os
 from copy import deepcopy
 
 import numpy as np
 import torch.utils.data
 
-from fsnet_amd.monodepth.data.datasets.utils import cam_relative_pose, read_depth, read_image, read_pose_mat
+from fsnet_amd.monodepth.data.datasets.utils import (cam_relative_pose, read_depth, read_flow_png, read_image,
+                                                      read_motion_mask, read_pose_mat)
 from fsnet_amd.vision_base.utils.builder import build
 from fsnet_amd.vision_base.utils.utils import EasyDict
 
@@ -90,8 +96,12 @@ class KittiDepthMonoDataset(torch.utils.data.Dataset):
                 T_imu2vel=read_imu2velo(os.path.join(folder_path, "calib_imu_to_velo.txt")))
         self.pose_dict = {key: read_pose_mat(os.path.join(self.raw_path, key, 'oxts', 'pose.mat'))
                           for key in set(obj['folder'] for obj in self.imdb)}
-        if getattr(data_cfg, 'is_motion_mask', False) or getattr(data_cfg, 'is_precompute_flow', False):
-            raise NotImplementedError("precomputed motion masks / flow are not part of the mirrored data path")
+        self.is_motion_mask = getattr(data_cfg, 'is_motion_mask', False)
+        self.is_precompute_flow = getattr(data_cfg, 'is_precompute_flow', False)
+        if self.is_motion_mask:
+            self.precompute_path = getattr(data_cfg, 'motion_mask_path', "")
+        if self.is_precompute_flow:
+            self.flow_path = getattr(data_cfg, 'flow_path', "")
         self.is_filter_static = getattr(data_cfg, 'is_filter_static', True)
         if self.is_filter_static:
             self.imdb = self._filter_static_indexes()
@@ -118,6 +128,10 @@ class KittiDepthMonoDataset(torch.utils.data.Dataset):
             data[('original_image', idx)] = data[('image', idx)].copy()
         h, w, _ = data[("image", 0)].shape
         data["patched_mask"] = np.ones([h, w])
+        if self.is_motion_mask:
+            data['motion_mask'] = self.get_motion_mask(i)
+        if self.is_precompute_flow:
+            data['flow'] = self.get_flow(i)
         for idx, pose in zip(self.frame_idxs[1:], self._relative_poses(folder, index, datetime)):
             data[('relative_pose', idx)] = pose
         data['P2'] = self.meta_dict[datetime][{"l": "P2", "r": "P3"}[side]]
@@ -140,3 +154,9 @@ class KittiDepthMonoDataset(torch.utils.data.Dataset):
 
     def get_pose(self, folder, frame_indexes, *args, **kwargs):
         return self.pose_dict[folder][frame_indexes, :, :]
+
+    def get_motion_mask(self, i):
+        return read_motion_mask(os.path.join(self.precompute_path, f"{i:08d}.png"))
+
+    def get_flow(self, i):
+        return read_flow_png(os.path.join(self.flow_path, f"{i:08d}.png"))

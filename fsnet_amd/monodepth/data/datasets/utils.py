@@ -34,3 +34,90 @@ def read_vo_depth(path):
     d[d < 3] = 120
     d[d > 80] = 120
     return d
+
+
+def read_motion_mask(path):
+    """[H, W] uint8 as written by the precompute hooks (reference mono_dataset.py:241-244 reads it with
+    cv2.imread(path, IMREAD_UNCHANGED))"""
+    return np.array(Image.open(path, 'r'))
+
+
+def read_png16(path):
+    """16-bit truecolour PNG (colour type 2, bit depth 16, not interlaced) -> uint16 [H, W, 3] in file channel order.
+    PIL opens such files as 8-bit RGB, so this decodes them with zlib: IHDR, the IDAT stream, filters 0-4.  Filters
+    None, Sub and Up are vectorised per row (a 375x1242 file in ~20 ms); Average and Paeth rows step one pixel at a
+    time in numpy (seconds for a 375x1242 file made only of them).  write_png16 writes filter 0."""
+    import struct
+    import zlib
+    with open(path, 'rb') as f:
+        blob = f.read()
+    if blob[:8] != b'\x89PNG\r\n\x1a\n':
+        raise ValueError("%s is not a PNG file" % path)
+    pos, idat, hdr = 8, [], None
+    while pos < len(blob):
+        n, kind = struct.unpack('>I4s', blob[pos:pos + 8])
+        body = blob[pos + 8:pos + 8 + n]
+        if kind == b'IHDR':
+            hdr = struct.unpack('>IIBBBBB', body)
+        elif kind == b'IDAT':
+            idat.append(body)
+        elif kind == b'IEND':
+            break
+        pos += 12 + n
+    W, H, depth, ctype, _, _, interlace = hdr
+    if depth != 16 or ctype != 2 or interlace != 0:
+        raise ValueError("%s: only 16-bit RGB non-interlaced PNGs are read here (bit depth %d, colour type %d)"
+                         % (path, depth, ctype))
+    bpp, stride = 6, W * 6
+    raw = np.frombuffer(zlib.decompress(b''.join(idat)), np.uint8).reshape(H, stride + 1)
+    out = np.zeros((H, stride), np.uint8)
+    prev = np.zeros(stride, np.int64)
+    for y in range(H):
+        ft, line = raw[y, 0], raw[y, 1:].astype(np.int64)
+        if ft == 0:
+            cur = line
+        elif ft == 1:        # Sub: a running sum along each of the 6 byte lanes
+            cur = np.cumsum(line.reshape(W, bpp), axis=0).reshape(-1) & 255
+        elif ft == 2:        # Up
+            cur = (line + prev) & 255
+        elif ft in (3, 4):   # Average / Paeth: sequential along the row, one pixel (6 lanes) per step
+            cur = np.zeros(stride, np.int64)
+            a = np.zeros(bpp, np.int64)
+            c = np.zeros(bpp, np.int64)
+            for x in range(0, stride, bpp):
+                b = prev[x:x + bpp]
+                if ft == 3:
+                    pr = (a + b) >> 1
+                else:
+                    pa, pb, pc = np.abs(b - c), np.abs(a - c), np.abs(a + b - 2 * c)
+                    pr = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+                a = (line[x:x + bpp] + pr) & 255
+                cur[x:x + bpp] = a
+                c = b
+        else:
+            raise ValueError("%s: PNG filter type %d" % (path, ft))
+        out[y] = cur
+        prev = cur
+    return out.reshape(H, W, 3, 2).astype(np.uint16) @ np.array([256, 1], np.uint16)
+
+
+def write_png16(path, img):
+    """uint16 [H, W, 3] -> 16-bit truecolour PNG (filter 0), the format read_png16 reads"""
+    import struct
+    import zlib
+    img = np.ascontiguousarray(np.asarray(img, '>u2'))
+    H, W, _ = img.shape
+    raw = b''.join(b'\x00' + img[y].tobytes() for y in range(H))
+
+    def chunk(kind, body):
+        return struct.pack('>I', len(body)) + kind + body + struct.pack('>I', zlib.crc32(kind + body) & 0xffffffff)
+    with open(path, 'wb') as f:
+        f.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', W, H, 16, 2, 0, 0, 0)) +
+                chunk(b'IDAT', zlib.compress(raw)) + chunk(b'IEND', b''))
+
+
+def read_flow_png(path):
+    """precomputed flow (reference mono_dataset.py:246-250): cv2.imread(path, IMREAD_UNCHANGED)[:, :, 0:2] is BGR,
+    i.e. the file's channels (2, 1); (v - 2^15) / 64 in fp32 -> [H, W, 2]"""
+    v = read_png16(path)[:, :, [2, 1]]
+    return (v.astype(np.float32) - 2 ** 15) / 64.0

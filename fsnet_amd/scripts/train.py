@@ -60,6 +60,9 @@ def main(argv=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.distributed.init_process_group(backend="nccl", init_method="env://")
 
+    if "precompute_hook" in cfg:                 # reference scripts/train.py:78-80 (e.g. MotionMaskPrecomputeHook)
+        precompute_hook = build(**cfg.precompute_hook)
+        precompute_hook()
     dataset_train = build(**cfg.train_dataset)
     dataloader_train = build_dataloader(dataset_train, num_workers=cfg.data.num_workers, batch_size=cfg.data.batch_size,
                                         collate_fn=collate_fn, local_rank=rank, world_size=world_size,

@@ -31,6 +31,22 @@ def _plan(data):
     return p
 
 
+def _extra_gt(data, keys, shape):
+    """ground-truth images other than the synthesised patched_mask (e.g. a precomputed 'motion_mask'): uint8 [H, W] of
+    the frame's size, kept raw for DeviceAugment, which samples them with the frames' plan (fs_augment_masks)"""
+    plan = _plan(data)
+    extra = plan.setdefault("gt_extra", [])
+    for key in keys:
+        if key == 'patched_mask' or key not in data:
+            continue
+        m = data[key]
+        if not (isinstance(m, np.ndarray) and m.dtype == np.uint8 and m.ndim == 2 and m.shape == tuple(shape[:2])):
+            raise TypeError("ground-truth image %r must be uint8 [H, W] of the frame's size, got %s %s" % (
+                key, getattr(m, "dtype", type(m)), getattr(m, "shape", "")))
+        if key not in extra:
+            extra.append(key)
+
+
 def _frame_shape(data, key):
     img = data[key]
     if not (isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.ndim == 3):
@@ -80,8 +96,6 @@ class Resize(object):
     Normalizes follow and `gt_image_keys` carries the patched mask (cv2.INTER_NEAREST)."""
     def __init__(self, size, preserve_aspect_ratio=True, force_pad=True, image_keys=['image'], calib_keys=[],
                  gt_image_keys=[], **kwargs):
-        if any(k != 'patched_mask' for k in gt_image_keys):
-            raise NotImplementedError("the only ground-truth image on the device path is 'patched_mask'")
         self.size, self.preserve_aspect_ratio, self.force_pad = size, preserve_aspect_ratio, force_pad
         self.image_keys, self.calib_keys, self.gt_image_keys = image_keys, calib_keys, list(gt_image_keys)
 
@@ -90,8 +104,9 @@ class Resize(object):
         plan = _plan(data)
         if plan["warp"] is not None or plan.get("resize") is not None or plan["ops"] or plan["mirror"]:
             raise NotImplementedError("Resize is the first (and only geometric) stage of a device pipeline")
+        _extra_gt(data, self.gt_image_keys, shape)
         for key in self.gt_image_keys:
-            if key in data:
+            if key == 'patched_mask' and key in data:
                 m = np.asarray(data[key])
                 if m.shape[:2] != tuple(shape[:2]) or not bool(np.all(m[::8, ::8] == 1)):
                     raise NotImplementedError("the device path resizes an all-ones patched_mask of the frame's size")
@@ -143,6 +158,7 @@ class RandomWarpAffine(object):
         scale = max(height, width) * self.rng.uniform(self.scale_lower, self.scale_upper)
         center_w = self.rng.integers(low=self.shift_border, high=width - self.shift_border)
         center_h = self.rng.integers(low=self.shift_border, high=height - self.shift_border)
+        _extra_gt(data, self.gt_image_keys, (height, width))
         final_scale = max(self.output_w, self.output_h) / scale
         shift_w = self.output_w / 2 - center_w * final_scale
         shift_h = self.output_h / 2 - center_h * final_scale
@@ -381,6 +397,9 @@ class DeviceAugment(object):
             r = p["resize"]
             if p["warp"] is not None or p["ops"] or p["mirror"] or (r["out_h"], r["out_w"]) != (r0["out_h"], r0["out_w"]):
                 raise NotImplementedError("a validation batch is Resize + Normalize with one output size")
+            if p.get("gt_extra"):
+                raise NotImplementedError("ground-truth images %r travel with a training Resize (gt_image_keys), not "
+                                          "the validation input" % (p["gt_extra"],))
             h, w = r["src_hw"]
             for f, idx in enumerate(self.frame_idxs):
                 src_np[b, f, :h, :w] = s[(self.image_family, idx)]
@@ -422,12 +441,30 @@ class DeviceAugment(object):
             self._colour_plan(p, iplan[b], fplan[b])
         batch = {PLAN: dict(src=src, dims=torch.from_numpy(dims), iplan=torch.from_numpy(iplan),
                             fplan=torch.from_numpy(fplan), mean=mean, std=std, out_hw=(r0["out_h"], r0["out_w"]),
-                            kind="resize", train=True, mask=bool(r0.get("gt_keys")))}
+                            kind="resize", train=True, mask='patched_mask' in r0.get("gt_keys", []))}
+        self._collate_gt(samples, plans, batch)
         self._collate_rest(samples, batch)
         return batch
 
+    @staticmethod
+    def _collate_gt(samples, plans, batch):
+        """the extra uint8 ground-truth images of the batch (_extra_gt), zero-padded to one [B, Hs, Ws] per key"""
+        keys = list(plans[0].get("gt_extra", []))
+        if any(list(p.get("gt_extra", [])) != keys for p in plans):
+            raise ValueError("samples of one batch must carry the same ground-truth images")
+        gt = {}
+        for key in keys:
+            Hs = max(s[key].shape[0] for s in samples)
+            Ws = max(s[key].shape[1] for s in samples)
+            t = torch.zeros(len(samples), Hs, Ws, dtype=torch.uint8)
+            for b, s in enumerate(samples):
+                h, w = s[key].shape
+                t.numpy()[b, :h, :w] = s[key]
+            gt[key] = t
+        batch[PLAN]["gt"] = gt
+
     def _collate_rest(self, samples, batch):
-        skip = {PLAN, self.mask_key}
+        skip = {PLAN, self.mask_key} | set(batch[PLAN].get("gt", {}))
         for idx in self.frame_idxs:
             skip.add((self.image_family, idx)); skip.add((self.original_family, idx))
         for key in samples[0]:
@@ -483,6 +520,7 @@ class DeviceAugment(object):
             iplan[b, 5], iplan[b, 6] = h, w
         batch = {PLAN: dict(src=src, minv=torch.from_numpy(minv), iplan=torch.from_numpy(iplan),
                             fplan=torch.from_numpy(fplan), mean=mean, std=std, out_hw=(out_h, out_w), kind="warp")}
+        self._collate_gt(samples, plans, batch)
         self._collate_rest(samples, batch)
         return batch
 
@@ -518,6 +556,7 @@ class DeviceAugment(object):
                     batch[(self.original_family, idx)] = original[f]
             if mask is not None:
                 batch[self.mask_key] = mask
+            self._materialize_gt(plan, batch, device, H, W, dims=dims, iplan=plan.get("train") and iplan)
             for key, val in list(batch.items()):
                 if isinstance(val, torch.Tensor) and not val.is_cuda:
                     batch[key] = val.to(device, non_blocking=True)
@@ -539,10 +578,21 @@ class DeviceAugment(object):
             batch[(self.image_family, idx)] = image[f]
             batch[(self.original_family, idx)] = original[f]
         batch[self.mask_key] = mask
+        self._materialize_gt(plan, batch, device, H, W, minv=minv, iplan=iplan)
         for key, val in list(batch.items()):
             if isinstance(val, torch.Tensor) and not val.is_cuda:
                 batch[key] = val.to(device, non_blocking=True)
         return batch
+
+    @staticmethod
+    def _materialize_gt(plan, batch, device, H, W, minv=None, dims=None, iplan=None):
+        """each extra ground-truth image through the frames' warp / resize and mirror: fp32 [B, H, W] on the device"""
+        if not plan.get("gt"):
+            return
+        from ....hip import ops
+        for key, src in plan["gt"].items():
+            batch[key] = ops.augment_masks(src.to(device, non_blocking=True), H, W, minv=minv, dims=dims,
+                                           iplan=iplan if iplan is not None and iplan is not False else None)
 
     def __call__(self, samples, device=None):
         return self.materialize(self.collate(samples), device)

@@ -33,6 +33,11 @@ class ConcatDataset(torch.utils.data.Dataset):
         super().__init__()
         from fsnet_amd.vision_base.utils.builder import build
         self.children = [build(**dict(common_keywords, **item)) for item in cfg_list]
+        if len(self.children) > 1 and any(getattr(c, 'is_motion_mask', False) or getattr(c, 'is_precompute_flow', False)
+                                          for c in self.children):
+            # the files are named by the child's own index, the precompute hook writes the concatenated index
+            raise ValueError("precomputed motion masks / flow (is_motion_mask, is_precompute_flow) need a single "
+                             "dataset: a ConcatDataset of several children would read another sample's file")
         lengths = [len(c) for c in self.children]
         self.seperator = np.concatenate([[0], np.cumsum(lengths[:-1])]).astype(np.int64)   # (the reference's spelling)
         self.total_length = int(sum(lengths))

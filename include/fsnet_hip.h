@@ -33,7 +33,7 @@ extern "C" {
 
 /* library/ABI version and the ISA the kernels were compiled for ("gfx950").  FS_ABI_VERSION changes whenever an
  * argument struct or a signature below does; a host binding refuses a library that reports another number. */
-#define FS_ABI_VERSION 12
+#define FS_ABI_VERSION 13
 int fs_abi_version(void);
 const char* fs_target_arch(void);
 /* debugging aid: writes the device's constant-rate clock (wall_clock64, 100 MHz) into *slot (u64) on `stream`;
@@ -373,6 +373,56 @@ typedef struct FsPostOptArgs {
 } FsPostOptArgs;
 int fs_postopt(const FsPostOptArgs* args, void* stream);
 int64_t fs_postopt_workspace_bytes(int B, int H, int W, int K);
+
+/* Dense Farneback optical flow (cv2.calcOpticalFlowFarneback as called by MotionMaskPrecomputeHook,
+ * base_precompute_hooks.py:27-89; OpenCV 4.x optflowgf.cpp restated in tests/helpers_optflow.py, parity with cv2
+ * unpinned): B frame pairs img0 / img1 [B][H][W][3] uint8 (converted to gray like cv2 BGR2GRAY with channel 0 as blue)
+ * -> flow [B][H][W][2] fp32 (x, y).  Fixed launch sequence, no host sync (capturable), no atomics (bit-identical from
+ * run to run and across batchings).  FS_EINVAL: H or W < 2, H*W >= 2^30, pyr_scale outside (0, 1), levels outside
+ * 0..15, winsize outside 1..129, iterations < 1, poly_n other than 5 / 7, poly_sigma < 0, flags other than 0 /
+ * OPTFLOW_FARNEBACK_GAUSSIAN (256) (OPTFLOW_USE_INITIAL_FLOW is not taken), a Gaussian pyramid blur wider than 255
+ * taps, workspace_bytes < fs_optflow_workspace_bytes(args) (which is -1 where fs_optflow_farneback would refuse the
+ * parameters). */
+typedef struct FsFlowArgs {
+  const uint8_t* img0;
+  const uint8_t* img1;
+  float* flow;
+  void* workspace;
+  int64_t workspace_bytes;
+  double pyr_scale;
+  double poly_sigma;
+  int32_t B, H, W, levels, winsize, iterations, poly_n, flags;
+} FsFlowArgs;
+int fs_optflow_farneback(const FsFlowArgs* args, void* stream);
+int64_t fs_optflow_workspace_bytes(const FsFlowArgs* args);
+/* one pyramid level of fs_optflow_farneback alone (the gray pair, its Gaussian blur and resize to level `level`,
+ * 0 = finest): out [B][2][h][w] fp32 with the level size of that call.  For checking the coarse levels, which the full
+ * call overwrites.  FS_EINVAL as fs_optflow_farneback, or a level outside 0..(levels actually used). */
+int fs_optflow_level_image(const FsFlowArgs* args, int level, float* out, void* stream);
+
+/* Epipolar motion mask (base_precompute_hooks.py:58-89 and :109-148): per sample F = K^-T [T]x R K^-1 in f64 from
+ * P2 [B][3][4] (K = P2[:3,:3]) and pose [B][4][4] (relative_pose, frame 0 -> 1), rounded to fp32; per pixel in fp32
+ * l = F [x y 1], d = [x+u y+v 1] . (l / |l_0:2|); mask [B][H][W] uint8 = |d| > threshold (mode 0, the Farneback hook)
+ * or |d| / |flow| > threshold (mode 1, the ARFlow hook; IEEE: a zero flow with d = 0 is not masked).  flow
+ * [B][H][W][2] fp32.  FS_EINVAL: mode other than 0 / 1, H*W >= 2^31. */
+typedef struct FsMotionMaskArgs {
+  const float* flow;
+  const double* P2;
+  const double* pose;
+  uint8_t* mask;
+  float threshold;
+  int32_t mode;
+  int32_t B, H, W;
+} FsMotionMaskArgs;
+int fs_motion_mask(const FsMotionMaskArgs* args, void* stream);
+
+/* Ground-truth masks (e.g. the precomputed motion_mask; mono_dataset.py:194-195, 241-244) through the plan of
+ * fs_augment_frames (minv + iplan: cv2.warpAffine INTER_NEAREST, BORDER_CONSTANT 0, then RandomMirror iplan[b][4];
+ * sample b's mask is the top-left iplan[b][5] x iplan[b][6] of src) or of fs_resize_frames (dims, iplan optional:
+ * cv2.resize INTER_NEAREST to rh x rw, zero pad / crop to H x W, mirror).  src [B][Hs][Ws] uint8 -> out [B][H][W] fp32.
+ * FS_EINVAL: both or neither of minv / dims, minv without iplan, H*W or Hs*Ws >= 2^31. */
+int fs_augment_masks(const uint8_t* src, const double* minv, const int32_t* dims, const int32_t* iplan, float* out,
+                     int B, int Hs, int Ws, int H, int W, void* stream);
 
 /* n <= FS_COPY_MAX device-to-device copies (16-byte aligned pointers, any byte counts) in one launch: the training
  * hook stages a batch into the static input buffers of its captured hipGraph with it

@@ -1042,7 +1042,64 @@ def gen_postopt():
     np.savez_compressed(os.path.join(GOLD, "postopt.npz"), **out)
 
 
+def gen_motion_mask():
+    """the REAL MotionMaskPrecomputeHook and MotionMaskARFlowPrecomputeHook (base_precompute_hooks.py:27-148) over a
+    helpers_kitti.make_tree tree of 96x320 frames (two pyramid levels), on CPU (Tensor.cuda is a no-op here), with
+    the cv2 shim's calcOpticalFlowFarneback (= the restatement of tests/helpers_optflow.py), BGR2GRAY, imwrite and
+    imread.  The ARFlow hook reads seeded flow PNGs through the REAL dataset (is_precompute_flow).  Records the written
+    files (names and masks), the samples' P2 / original_P2 / relative poses, and a checksum of the Farneback flows;
+    the frames and flow files are regenerated from their seeds by the test."""
+    import tempfile
+    from PIL import Image
+    from tests import helpers_kitti as HK
+    from tests import helpers_optflow as HO
+    from monodepth.pipeline_hooks.precomputing_hooks.base_precompute_hooks import (
+        MotionMaskARFlowPrecomputeHook, MotionMaskPrecomputeHook)
+    H, W = HO.GOLDEN_HW
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        raw, split = HK.make_tree(d, seed=HO.GOLDEN_TREE_SEED, H=H, W=W)
+        cfg = HO.raw_dataset_cfg(raw, split, prefix='')
+        for tag, fcfg in (("box", HO.GOLDEN_FLOW_CFG), ("gauss", HO.GOLDEN_FLOW_CFG_G)):
+            odir = os.path.join(d, "mm_" + tag)
+            os.makedirs(odir)
+            hook = MotionMaskPrecomputeHook(cfg, fcfg, distance_threshold=HO.GOLDEN_THR[0], output_dir=odir)
+            hook()
+            names = sorted(os.listdir(odir))
+            out["%s_names" % tag] = np.array(names)
+            out["%s_masks" % tag] = np.stack([np.array(Image.open(os.path.join(odir, f))) for f in names])
+            sums = []
+            for i in range(len(hook.dataset)):
+                smp = hook.dataset[i]
+                g0, g1 = HO.gray(smp[("image", 0)]), HO.gray(smp[("image", 1)])
+                sums.append(float(np.abs(HO.farneback(g0, g1, **fcfg)).astype(np.float64).sum()))
+            out["%s_flow_abs_sum" % tag] = np.array(sums)
+        n = len(hook.dataset)
+        for i in range(n):
+            smp = hook.dataset[i]
+            out["s%d_P2" % i] = np.asarray(smp["P2"], np.float64)
+            out["s%d_original_P2" % i] = np.asarray(smp["original_P2"], np.float64)
+            out["s%d_pose" % i] = np.asarray(smp[("relative_pose", 1)])
+        fdir = os.path.join(d, "flow")
+        HO.write_flow_pngs(fdir, n, H, W)
+        acfg = dict(cfg, is_precompute_flow=True, flow_path=fdir)
+        odir = os.path.join(d, "mm_arflow")
+        os.makedirs(odir)
+        MotionMaskARFlowPrecomputeHook(acfg, {}, distance_threshold=HO.GOLDEN_THR[1], output_dir=odir)()
+        names = sorted(os.listdir(odir))
+        out["arflow_names"] = np.array(names)
+        out["arflow_masks"] = np.stack([np.array(Image.open(os.path.join(odir, f))) for f in names])
+    out["n"] = np.int64(n)
+    for tag in ("box", "gauss", "arflow"):
+        print("motion mask %s: %d files, %.4f of the pixels masked" % (tag, len(out[tag + "_names"]),
+                                                                        float(out[tag + "_masks"].mean())))
+    np.savez_compressed(os.path.join(GOLD, "motion_mask.npz"), **out)
+
+
 if __name__ == "__main__":
+    if "--only-motion-mask" in sys.argv:
+        gen_motion_mask()
+        sys.exit(0)
     if "--only-postopt" in sys.argv:
         gen_postopt()
         sys.exit(0)
@@ -1104,5 +1161,6 @@ if __name__ == "__main__":
     gen_no_overlap_mask()
     gen_velo_gt()
     gen_postopt()
+    gen_motion_mask()
     for f in sorted(os.listdir(GOLD)):
         print(f, os.path.getsize(os.path.join(GOLD, f)) // 1024, "KiB")
