@@ -4,6 +4,7 @@
 //   cv2.resize(..., INTER_LINEAR) of the (inverse) depth     monodepth/pipeline_hooks/evaluation_hooks/base_evaluation_hooks.py:57
 //                                                            monodepth/evaluation/kitti_unsupervised_eval.py:49
 //   mask / Garg crop / median ratio / clamp                  kitti_unsupervised_eval.py:50-74
+//   fisheye mask (0.3 < gt < 60, close mask, no crop)        monodepth/evaluation/kitti360_fisheye_eval.py:43-72
 //   compute_errors (abs_rel, sq_rel, rmse, rmse_log, a1-a3)  monodepth/networks/utils/monodepth_utils.py:271-289
 // cv2 is a third-party dependency that is absent from the reference tree: its INTER_LINEAR rule for
 // single-channel float images is restated here from OpenCV's resize.cpp (pixel centres at (x+0.5)*scale-0.5, floor,
@@ -55,8 +56,15 @@ struct EvalCtx {
   int y0, y1, x0, x1;     // Garg crop
 };
 
-// k-th smallest (0-based) of v[0..n): 4 passes over 8-bit digits of the float bit pattern (all values are positive,
-// so the patterns order like the floats).  v = interleaved pairs, element `which`.
+// k-th smallest (0-based) of v[0..n): 4 passes over 8-bit digits of the float bit pattern.  v = interleaved pairs,
+// element `which`.  SIGNED = false: all values are positive, so the raw patterns order like the floats (fs_depth_eval:
+// the KITTI network's depth is positive).  SIGNED = true (fs_depth_eval_masked): the patterns are first mapped to keys
+// that order like the floats for either sign — a fisheye prediction is Z x norm and is negative where the ray table is
+// invalid, and the inverse-depth resize can carry such values next to valid ground truth (np.median orders them too).
+__device__ __forceinline__ unsigned float_key(unsigned u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ unsigned key_float(unsigned k) { return (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; }
+
+template <bool SIGNED>
 __device__ float radix_select(const float2* __restrict__ v, long n, int which, long k, unsigned* hist,
                               unsigned* s_prefix, long* s_k) {
   unsigned prefix = 0, mask = 0;
@@ -66,6 +74,7 @@ __device__ float radix_select(const float2* __restrict__ v, long n, int which, l
     for (long i = threadIdx.x; i < n; i += blockDim.x) {
       float2 e = v[i];
       unsigned u = __float_as_uint(which ? e.y : e.x);
+      if (SIGNED) u = float_key(u);
       if ((u & mask) == prefix) atomicAdd(&hist[(u >> shift) & 255u], 1u);
     }
     __syncthreads();
@@ -78,7 +87,7 @@ __device__ float radix_select(const float2* __restrict__ v, long n, int which, l
     prefix = *s_prefix; k = *s_k; mask |= 255u << shift;
     __syncthreads();
   }
-  return __uint_as_float(prefix);
+  return __uint_as_float(SIGNED ? key_float(prefix) : prefix);
 }
 
 __device__ void error_sums(const float2* __restrict__ v, long n, float ratio, double* acc /*7*/, double* sh) {
@@ -108,10 +117,15 @@ __device__ void error_sums(const float2* __restrict__ v, long n, float ratio, do
   }
 }
 
-// out[b][16] = { ratio, err[7] (median-scaled), abs_err[7] (unscaled), n_valid }; scratch[b] holds up to H*W pairs
+// out[b][16] = { ratio, err[7] (median-scaled), abs_err[7] (unscaled), n_valid }; scratch[b] holds up to H*W pairs.
+// MASKED = false is fs_depth_eval (KITTI: 1e-3 < gt < 80 inside the Garg crop, the constants written in); MASKED = true
+// is fs_depth_eval_masked: lo < gt < hi, the crop only when asked for, and mask[b][y][x] != 0 when a mask is given
+// (the fisheye evaluation: 0.3 < gt < 60 and the close mask, no crop; kitti360_fisheye_eval.py:43-72).
+template <bool MASKED>
 __global__ __launch_bounds__(1024) void depth_eval_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                           int B, int h, int w, int H, int W, float2* __restrict__ scratch,
-                                                          double* __restrict__ out) {
+                                                          double* __restrict__ out, float lo, float hi, int crop,
+                                                          const uint8_t* __restrict__ mask) {
   __shared__ unsigned hist[256];
   __shared__ unsigned s_prefix;
   __shared__ long s_k;
@@ -123,14 +137,17 @@ __global__ __launch_bounds__(1024) void depth_eval_kernel(const float* __restric
   const float* g0 = gt + (long)b * H * W;
   float2* v = scratch + (long)b * H * W;
   // float64 like numpy: in float32 0.99189189 * 370 rounds up to 367.0 and the crop gains a row
-  const int y0 = (int)(0.40810811 * (double)H), y1 = (int)(0.99189189 * (double)H);
-  const int x0 = (int)(0.03594771 * (double)W), x1 = (int)(0.96405229 * (double)W);
+  const bool garg = !MASKED || crop != 0;
+  const int y0 = garg ? (int)(0.40810811 * (double)H) : 0, y1 = garg ? (int)(0.99189189 * (double)H) : H;
+  const int x0 = garg ? (int)(0.03594771 * (double)W) : 0, x1 = garg ? (int)(0.96405229 * (double)W) : W;
+  const uint8_t* m0 = MASKED && mask ? mask + (long)b * H * W : nullptr;
   if (threadIdx.x == 0) s_n = 0;
   __syncthreads();
   for (int y = y0; y < y1; ++y)
     for (int x = x0 + threadIdx.x; x < x1; x += blockDim.x) {
       const float g = g0[(long)y * W + x];
-      if (g > 1e-3f && g < 80.0f) {
+      const bool in_range = MASKED ? (g > lo && g < hi && (!m0 || m0[(long)y * W + x] != 0)) : (g > 1e-3f && g < 80.0f);
+      if (in_range) {
         const float p = resample(pr, h, w, H, W, y, x, false);
         v[atomicAdd(&s_n, 1u)] = make_float2(g, p);       // order is irrelevant to medians and sums
       }
@@ -142,8 +159,8 @@ __global__ __launch_bounds__(1024) void depth_eval_kernel(const float* __restric
   // np.median: mean of the two middle order statistics (in the array's float32)
   float med[2];
   for (int which = 0; which < 2; ++which) {
-    float lo = radix_select(v, n, which, (n - 1) / 2, hist, &s_prefix, &s_k);
-    float hi = (n & 1) ? lo : radix_select(v, n, which, n / 2, hist, &s_prefix, &s_k);
+    float lo = radix_select<MASKED>(v, n, which, (n - 1) / 2, hist, &s_prefix, &s_k);
+    float hi = (n & 1) ? lo : radix_select<MASKED>(v, n, which, n / 2, hist, &s_prefix, &s_k);
     med[which] = (lo + hi) * 0.5f;
   }
   const float ratio = med[0] / med[1];
@@ -174,7 +191,15 @@ extern "C" int fs_resize_linear(const float* src, float* dst, int h, int w, int 
 extern "C" int fs_depth_eval(const float* pred, const float* gt, int B, int h, int w, int H, int W, void* scratch,
                              double* out16, void* stream) {
   if (!pred || !gt || !scratch || !out16 || B < 1 || h < 1 || w < 1 || H < 2 || W < 2) return FS_EINVAL;
-  hipLaunchKernelGGL(depth_eval_kernel, dim3(B), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), pred, gt, B, h, w, H,
-                     W, static_cast<float2*>(scratch), out16);
+  hipLaunchKernelGGL(depth_eval_kernel<false>, dim3(B), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), pred, gt, B,
+                     h, w, H, W, static_cast<float2*>(scratch), out16, 1e-3f, 80.0f, 1, nullptr);
+  return fs_launch_status();
+}
+
+extern "C" int fs_depth_eval_masked(const float* pred, const float* gt, const uint8_t* mask, int B, int h, int w, int H,
+                                    int W, float lo, float hi, int crop, void* scratch, double* out16, void* stream) {
+  if (!pred || !gt || !scratch || !out16 || B < 1 || h < 1 || w < 1 || H < 2 || W < 2 || !(lo < hi)) return FS_EINVAL;
+  hipLaunchKernelGGL(depth_eval_kernel<true>, dim3(B), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), pred, gt, B,
+                     h, w, H, W, static_cast<float2*>(scratch), out16, lo, hi, crop, mask);
   return fs_launch_status();
 }

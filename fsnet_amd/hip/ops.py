@@ -763,6 +763,71 @@ def depth_eval(pred, gt):
     return out
 
 
+def depth_eval_masked(pred, gt, mask=None, lo=0.3, hi=60.0, crop=False):
+    """depth_eval with the valid set as arguments (fs_depth_eval_masked): lo < gt < hi (compared in float32, as numpy
+    compares a float32 array with a Python float), the Garg crop when `crop`, and mask != 0 when a uint8 / bool mask
+    [B, H, W] is given.  Defaults: the fisheye evaluation (kitti360_fisheye_eval.py:43-72).  Returns f64 [B, 16]."""
+    assert pred.is_cuda and gt.is_cuda and pred.dtype == gt.dtype == torch.float32
+    assert pred.dim() == 3 and gt.dim() == 3 and pred.shape[0] == gt.shape[0]
+    pred, gt = pred.contiguous(), gt.contiguous()
+    if mask is not None:
+        assert mask.is_cuda and tuple(mask.shape) == tuple(gt.shape) and mask.dtype in (torch.uint8, torch.bool)
+        mask = mask.contiguous().view(torch.uint8)
+    out = torch.empty(pred.shape[0], 16, dtype=torch.float64, device=pred.device)
+    scratch = torch.empty(gt.numel() * 2, dtype=torch.float32, device=pred.device)
+    check(lib.fs_depth_eval_masked(pred.data_ptr(), gt.data_ptr(), _p(mask), pred.shape[0], pred.shape[1],
+                                   pred.shape[2], gt.shape[1], gt.shape[2], float(lo), float(hi), int(bool(crop)),
+                                   scratch.data_ptr(), out.data_ptr(), stream_ptr()), "depth_eval_masked")
+    return out
+
+
+class LidarMeiDepth:
+    """LiDAR ground truth through the Mei fisheye model, G frames per call (fs_lidar_mei_depth;
+    kitti360_fisheye_eval.py:97-145).  Buffers are kept between calls of the same (G, H, W) so that a call can be
+    captured into a graph and replayed: stage() copies the inputs into them, run() issues the kernels only."""
+
+    def __init__(self, G, H, W, device):
+        self.G, self.H, self.W, self.device = G, H, W, torch.device(device)
+        ws = int(lib.fs_lidar_mei_depth_workspace_bytes(G, H, W))
+        if ws < 0:
+            raise ValueError("lidar_mei_depth: bad shape G=%d H=%d W=%d" % (G, H, W))
+        self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+        self.offsets = torch.zeros(G + 1, dtype=torch.int64, device=self.device)
+        self.T = torch.zeros(G, 16, dtype=torch.float64, device=self.device)
+        self.mei = torch.zeros(G, 7, dtype=torch.float64, device=self.device)
+        self.depth = torch.empty(G, H, W, dtype=torch.float32, device=self.device)
+        self.close_mask = torch.empty(G, H, W, dtype=torch.uint8, device=self.device)
+        self.points = torch.empty(0, 4, dtype=torch.float32, device=self.device)
+
+    def stage(self, scans, T, mei):
+        """scans: G float32 [Ni, 4] arrays / tensors; T: f64 [G, 4, 4]; mei: f64 [G, 7] = gamma1 gamma2 u0 v0 k1 k2 xi"""
+        import numpy as np
+        assert len(scans) == self.G
+        counts = [int(s.shape[0]) for s in scans]
+        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        pts = torch.cat([torch.as_tensor(np.asarray(s, dtype=np.float32).reshape(-1, 4)) for s in scans])
+        if self.points.shape[0] != pts.shape[0]:
+            self.points = torch.empty(pts.shape[0], 4, dtype=torch.float32, device=self.device)
+        self.points.copy_(pts)
+        self.offsets.copy_(torch.from_numpy(offs))
+        self.T.copy_(torch.from_numpy(np.asarray(T, dtype=np.float64).reshape(self.G, 16)))
+        self.mei.copy_(torch.from_numpy(np.asarray(mei, dtype=np.float64).reshape(self.G, 7)))
+
+    def run(self):
+        check(lib.fs_lidar_mei_depth(_p(self.points) if self.points.numel() else None, self.offsets.data_ptr(),
+                                     int(self.points.shape[0]), self.T.data_ptr(), self.mei.data_ptr(), self.G, self.H,
+                                     self.W, self.depth.data_ptr(), self.close_mask.data_ptr(),
+                                     self.workspace.data_ptr(), self.workspace.numel(), stream_ptr()), "lidar_mei_depth")
+        return self.depth, self.close_mask
+
+
+def lidar_mei_depth(scans, T, mei, H, W, device):
+    """one call: G = len(scans) frames -> (depth fp32 [G, H, W], close_mask uint8 [G, H, W]) on `device`"""
+    op = LidarMeiDepth(len(scans), H, W, device)
+    op.stage(scans, T, mei)
+    return op.run()
+
+
 _CENTRE_TABLES = {}
 
 

@@ -41,6 +41,10 @@ SIGNATURES = {
     "fs_distill_bwd": (C.c_int, [P, P, P, L, P, P, P, P]),
     "fs_resize_linear": (C.c_int, [P, P, I, I, I, I, I, P]),
     "fs_depth_eval": (C.c_int, [P, P, I, I, I, I, I, P, P, P]),
+    # ABI 14: Kitti360FisheyeEvaluator._single_loss (kitti360_fisheye_eval.py:43-72) and _precompute (:97-145)
+    "fs_depth_eval_masked": (C.c_int, [P, P, P, I, I, I, I, I, F, F, I, P, P, P]),
+    "fs_lidar_mei_depth": (C.c_int, [P, P, L, P, P, I, I, I, P, P, P, L, P]),
+    "fs_lidar_mei_depth_workspace_bytes": (C.c_int64, [I, I, I]),
     "fs_postopt": (C.c_int, [P, P]),
     "fs_postopt_workspace_bytes": (C.c_int64, [I, I, I, I]),
     "fs_optflow_farneback": (C.c_int, [P, P]),

@@ -1,6 +1,6 @@
 """File readers of the KITTI raw layout with the reference's names (monodepth/data/datasets/utils.py:22-54):
 PNG decode through PIL exactly like the reference's read_image, 16-bit ground-truth depth / 256, the MATLAB-devkit
-pose file, and the camera-frame relative pose."""
+pose file, velodyne scans, and the camera-frame relative poses."""
 import numpy as np
 import scipy.io as sio
 from PIL import Image
@@ -19,6 +19,17 @@ def read_depth(path):
 def read_pose_mat(path):
     """[N, 4, 4] imu-to-world poses written by the MATLAB devkit (reference :42-50)"""
     return sio.loadmat(path)['pose_mat']
+
+
+def read_pc_from_bin(bin_path):
+    """velodyne scan: float32 [N, 4] = x, y, z, reflectance (reference :8-11)"""
+    return np.fromfile(bin_path, dtype=np.float32).reshape(-1, 4)
+
+
+def cam_relative_pose_nusc(T_imu2world_0, T_imu2world_1, T_imu2cam):
+    """pose of camera frame 0 expressed in camera frame 1 from imu-to-world poses and one imu-to-camera transform
+    (reference :56-57; the KITTI-360 fisheye reader passes inv(T_cam2pose))"""
+    return T_imu2cam @ np.linalg.inv(T_imu2world_1) @ T_imu2world_0 @ np.linalg.inv(T_imu2cam)
 
 
 def cam_relative_pose(T_imu2world_0, T_imu2world_1, T_imu2vel, T_vel2cam):

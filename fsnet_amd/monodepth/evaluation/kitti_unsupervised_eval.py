@@ -79,6 +79,11 @@ class KittiEigenEvaluator(object):
             self.device or torch.device("cuda", torch.cuda.current_device()))
         return self._single_loss(depth_0, self._gt(index, dev))
 
+    def device_errors(self, depth_0, index):
+        """f64 [16] on the device: ratio, err[7], abs_err[7], n_valid of frame `index` (fs_depth_eval) — what the
+        evaluation hooks collect; each evaluator supplies its own metric here"""
+        return ops.depth_eval(depth_0[None], self._gt(index, depth_0.device)[None])[0]
+
     def log(self, writer, mean_errors, mean_abs_errors, global_step=0, epoch_num=0, is_print=True):
         log_str = f"Epoch {epoch_num}"
         log_str += "\n  " + ("{:>8} | " * 7).format("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")

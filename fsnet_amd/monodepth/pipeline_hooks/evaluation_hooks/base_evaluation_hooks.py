@@ -2,7 +2,9 @@
 (monodepth/pipeline_hooks/evaluation_hooks/base_evaluation_hooks.py:19-67): eval-mode forward over the validation set,
 crop to the effective size, inverse-depth resize to the original image size, per-image errors, mean + log.
 Everything between the network output and the 15 numbers per image stays on the device (fs_resize_linear with
-invert, fs_depth_eval); only those numbers are copied back.  KittiEvaluationHook_postopt (:69-127) refines the
+invert, then the evaluator's device_errors: fs_depth_eval for KITTI, fs_depth_eval_masked for the KITTI-360 fisheye
+evaluator); only those numbers are copied back.  Samples of the mirrored augmentation classes (raw frames plus a
+device plan, e.g. KITTI360FisheyeDataset with its validation Resize) are collated and resized by DeviceAugment.  KittiEvaluationHook_postopt (:69-127) refines the
 prediction with sparse visual-odometry depth first (ops.post_optimize, one call per batch on the device)."""
 import numpy as np
 import torch
@@ -10,8 +12,36 @@ from torch.utils.data import DataLoader
 
 from fsnet_amd.hip import ops
 from fsnet_amd.monodepth.networks.utils import postopt_utils as PU
+from fsnet_amd.vision_base.data.augmentations.augmentations import PLAN, DeviceAugment
 from fsnet_amd.vision_base.data.datasets.dataset_utils import collate_fn
 from fsnet_amd.vision_base.utils.builder import build
+
+
+def _collate(samples):
+    """collate_fn, or DeviceAugment.collate for samples of the mirrored augmentation classes (a validation Resize
+    plan: the frames it names are resized on the device by _materialize)"""
+    if PLAN not in samples[0]:
+        return collate_fn(samples)
+    keys = (samples[0][PLAN].get("resize") or {}).get("keys", [('image', 0)])
+    idxs = [k[1] for k in keys if isinstance(k, tuple) and k[0] == 'image']
+    batch = DeviceAugment(idxs).collate(samples)
+    batch[PLAN]["frame_idxs"] = idxs
+    return batch
+
+
+def _materialize(batched_data):
+    if PLAN in batched_data:
+        return DeviceAugment(batched_data[PLAN]["frame_idxs"]).materialize(batched_data)
+    return batched_data
+
+
+def _original_hw(batched_data, i):
+    """the size of the image before the validation Resize: ('original_image', 0) as in the reference, or the
+    ('image_resize', 'original_shape') the Resize records (a validation chain without a Copy, such as
+    configs/kitti360_fisheye_example's, carries no original image)"""
+    if ('original_image', 0) in batched_data:
+        return tuple(int(v) for v in batched_data[('original_image', 0)][i].shape[:2])
+    return tuple(int(v) for v in batched_data[('image_resize', 'original_shape')][i])
 
 
 class KittiEvaluationHook(object):
@@ -26,20 +56,20 @@ class KittiEvaluationHook(object):
         meta_arch.eval()
         batch_size = getattr(self, 'batch_size', 1)
         num_workers = getattr(self, 'num_workers', 4)
-        dataloader = DataLoader(dataset_val, batch_size, shuffle=False, num_workers=num_workers, collate_fn=collate_fn)
+        dataloader = DataLoader(dataset_val, batch_size, shuffle=False, num_workers=num_workers, collate_fn=_collate)
         rows = []
         frame_index = 0
         for batched_data in dataloader:
+            batched_data = _materialize(batched_data)
             output_dict = self.test_hook(batched_data, meta_arch, global_step, epoch_num)
             depth_b = output_dict['depth']
             for i in range(depth_b.shape[0]):
                 depth = depth_b[i, 0]
                 h_eff, w_eff = (int(v) for v in batched_data[('image_resize', 'effective_size')][i])
                 depth = depth[0:h_eff, 0:w_eff].float().contiguous()
-                h, w = (int(v) for v in batched_data[('original_image', 0)][i].shape[:2])
+                h, w = _original_hw(batched_data, i)
                 depth_0 = ops.resize_linear(depth, h, w, invert=True)          # 1 / cv2.resize(1 / depth, (w, h))
-                gt = self.dataset_eval_func._gt(frame_index, depth_0.device)
-                rows.append(ops.depth_eval(depth_0[None], gt[None])[0])
+                rows.append(self.dataset_eval_func.device_errors(depth_0, frame_index))
                 frame_index += 1
         res = torch.stack(rows).cpu().numpy()
         if (res[:, 15] == 0).any():
@@ -96,11 +126,12 @@ class KittiEvaluationHook_postopt(KittiEvaluationHook):
         params, vo_path = self._post_opt_params()
         batch_size = getattr(self, 'batch_size', 1)
         num_workers = getattr(self, 'num_workers', 4)
-        dataloader = DataLoader(dataset_val, batch_size, shuffle=False, num_workers=num_workers, collate_fn=collate_fn)
+        dataloader = DataLoader(dataset_val, batch_size, shuffle=False, num_workers=num_workers, collate_fn=_collate)
         rows = []
         frame_index = 0
         n_refined = n_unrefined = 0
         for batched_data in dataloader:
+            batched_data = _materialize(batched_data)
             output_dict = self.test_hook(batched_data, meta_arch, global_step, epoch_num)
             depth_b = output_dict['depth']
             image_b = batched_data[('image', 0)]
@@ -124,10 +155,9 @@ class KittiEvaluationHook_postopt(KittiEvaluationHook):
                     crops[t[0]] = refined[j]
                 n_refined += len(items)
             for i in range(B):
-                h, w = (int(v) for v in batched_data[('original_image', 0)][i].shape[:2])
+                h, w = _original_hw(batched_data, i)
                 depth_0 = ops.resize_linear(crops[i], h, w, invert=True)          # 1 / cv2.resize(1 / depth, (w, h))
-                gt = self.dataset_eval_func._gt(frame_index, depth_0.device)
-                rows.append(ops.depth_eval(depth_0[None], gt[None])[0])
+                rows.append(self.dataset_eval_func.device_errors(depth_0, frame_index))
                 frame_index += 1
         res = torch.stack(rows).cpu().numpy()
         if (res[:, 15] == 0).any():

@@ -33,7 +33,7 @@ extern "C" {
 
 /* library/ABI version and the ISA the kernels were compiled for ("gfx950").  FS_ABI_VERSION changes whenever an
  * argument struct or a signature below does; a host binding refuses a library that reports another number. */
-#define FS_ABI_VERSION 13
+#define FS_ABI_VERSION 14
 int fs_abi_version(void);
 const char* fs_target_arch(void);
 /* debugging aid: writes the device's constant-rate clock (wall_clock64, 100 MHz) into *slot (u64) on `stream`;
@@ -343,6 +343,28 @@ int fs_resize_frames(const FsResizeArgs* args, void* stream);
 int fs_resize_linear(const float* src, float* dst, int h, int w, int H, int W, int invert, void* stream);
 int fs_depth_eval(const float* pred, const float* gt, int B, int h, int w, int H, int W, void* scratch,
                   double* out16, void* stream);
+/* fs_depth_eval_masked (ABI 14): fs_depth_eval with the valid set as arguments — lo < gt < hi, the Garg crop only when
+ * crop != 0, and mask[b][y][x] != 0 when mask ([B][H][W] uint8) is not NULL.  The clamp to [1e-3, 80] and the metrics
+ * are fs_depth_eval's.  Kitti360FisheyeEvaluator._single_loss (kitti360_fisheye_eval.py:43-72) is lo = 0.3f,
+ * hi = 60, crop = 0, mask = the close mask.  FS_EINVAL unless lo < hi. */
+int fs_depth_eval_masked(const float* pred, const float* gt, const uint8_t* mask, int B, int h, int w, int H, int W,
+                         float lo, float hi, int crop, void* scratch, double* out16, void* stream);
+
+/* LiDAR ground truth of the KITTI-360 fisheye evaluation (ABI 14; Kitti360FisheyeEvaluator._precompute,
+ * kitti360_fisheye_eval.py:97-145, with MeiCameraProjection.cam2image, mei_fisheye_utils.py:23-51,135-137).
+ * G frames per call.  points: the G scans back to back, float32 [n_points][4] (x, y, z, reflectance); frame g owns
+ * points offsets[g] .. offsets[g+1] (offsets: device int64 [G+1], offsets[0] = 0, offsets[G] = n_points).
+ * T: device f64 [G][4][4] velodyne -> camera; mei: device f64 [G][7] = gamma1, gamma2, u0, v0, k1, k2, xi.
+ * Every point with camera z > 0 is projected in f64 in _cam2image's operation order; a point whose truncated pixel
+ * index falls outside [0, W) x [0, H) is dropped (the reference would fail or wrap the index).  Of the points that hit a
+ * pixel, the last in scan order wins (numpy's fancy assignment).  depth [G][H][W] fp32 = the winner's camera z, 0 where
+ * no point lands; close_mask [G][H][W] uint8 = 0 < norm < 8 of the winner.  workspace: at least
+ * fs_lidar_mei_depth_workspace_bytes(G, H, W) bytes (the int32 winner planes).  No host sync: capturable.
+ * Deterministic: the same bits for any run and any grouping of frames into calls. */
+int fs_lidar_mei_depth(const float* points, const int64_t* offsets, int64_t n_points, const double* T,
+                       const double* mei, int G, int H, int W, float* depth, uint8_t* close_mask, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int64_t fs_lidar_mei_depth_workspace_bytes(int G, int H, int W);
 
 /* Sparse-VO depth post-optimisation (postopt_utils.py:8-11, 94-226; KittiEvaluationHook_postopt,
  * base_evaluation_hooks.py:69-127), B images in one fixed launch sequence (capturable: no host sync, the launch count

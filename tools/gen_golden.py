@@ -682,6 +682,98 @@ def gen_kitti_dataset():
     np.savez_compressed(os.path.join(GOLD, "kitti_dataset.npz"), **out)
 
 
+def gen_kitti360_fisheye():
+    """the REAL KITTI360FisheyeDataset (fisheye_dataset.py:107-262) and Kitti360FisheyeEvaluator
+    (kitti360_fisheye_eval.py:15-145) over the seeded fake KITTI-360 tree of tests/helpers_kitti360.py: filtered index
+    lists, frames, P2 / original_P2 / calib_meta / patched_mask, relative poses (static filter on and off, left only
+    and seeded right images), the ground-truth maps of _precompute (stored as flat indices + values) and _single_loss on
+    seeded predictions.
+
+    Repair 1: MeiCameraProjection.cam2image (mei_fisheye_utils.py:135-137) torch.stack-s the numpy arrays _cam2image
+    returns for a numpy input and raises TypeError; here it is np.stack([x, y, z], -1) of the same three arrays.
+    The dataset reads its fisheye mask from a hard-coded path (fisheye_dataset.py:161-163): the cv2 shim's imread
+    serves the fixture mask for that path.  Both fixture conditions are asserted: every point with z > 0 projects
+    inside the image, and no two points share the reference's float sub2ind value (so its duplicate search is idle)."""
+    import hashlib
+    import json
+    import tempfile
+    import cv2
+    from tests import helpers_kitti360 as HK
+    mean, std = np.array([0.485, 0.456, 0.406], np.float32), np.array([0.229, 0.224, 0.225], np.float32)
+    from monodepth.data.datasets.fisheye_dataset import KITTI360FisheyeDataset
+    from monodepth.networks.utils import mei_fisheye_utils as MU
+    from monodepth.evaluation.kitti360_fisheye_eval import Kitti360FisheyeEvaluator
+    MU.MeiCameraProjection.cam2image = lambda self, points, P, calib: np.stack(list(MU._cam2image(points, P, calib)), -1)
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        raw, train, val, mask_path = HK.make_tree(d)
+        imread = cv2.imread
+        cv2.imread = lambda path, flags=1: imread(mask_path if path.endswith("kitti360_trainsub/fisheye_mask.png")
+                                                  else path, flags)
+        cases = dict(static_left=dict(is_filter_static=True, use_right_image=False, seed=None),
+                     all_left=dict(is_filter_static=False, use_right_image=False, seed=None),
+                     static_right=dict(is_filter_static=True, use_right_image=True, seed=3, fisheye_mask=mask_path))
+        for tag, c in cases.items():
+            kw = {k: v for k, v in c.items() if k != "seed"}
+            ds = KITTI360FisheyeDataset(**HK.dataset_cfg(raw, train, prefix='', **kw))
+            out[tag + "_index"] = np.array([o["img_indexes"] + o["pose_indexes"] for o in ds.imdb], np.int64)
+            if c["seed"] is not None:
+                np.random.seed(c["seed"])
+            for i in range(len(ds)):
+                smp = ds[i]
+                k = "%s_s%d_" % (tag, i)
+                for f in (0, -1, 1):
+                    # the frames are random bytes: stored as the sha256 of the uint8 frame the reference normalised
+                    img = npy(smp[("image", f)])
+                    u8 = np.round((img.transpose(1, 2, 0) * std + mean) * 255).astype(np.uint8)
+                    assert np.abs(((u8.astype(np.float32) / 255 - mean) / std).transpose(2, 0, 1) - img).max() < 1e-5
+                    out[k + "image_%d" % f] = np.array(hashlib.sha256(np.ascontiguousarray(u8).tobytes()).hexdigest())
+                out[k + "pose_m"] = np.asarray(smp[("relative_pose", -1)])
+                out[k + "pose_p"] = np.asarray(smp[("relative_pose", 1)])
+                out[k + "P2"], out[k + "original_P2"] = npy(smp["P2"]), np.asarray(smp["original_P2"])
+                out[k + "calib_meta"] = np.array(json.dumps(smp["calib_meta"], sort_keys=True))
+                pm = smp["patched_mask"]
+                out[k + "patched_mask"] = (npy(pm) if isinstance(pm, torch.Tensor) else np.asarray(pm)).astype(np.uint8)
+        cv2.imread = imread
+        # ground truth: the fixture conditions, then the real _precompute
+        from monodepth.data.datasets.fisheye_dataset import read_fisheycalib, extract_P_from_fisheye_calib
+        from monodepth.data.datasets.utils import read_pc_from_bin
+        calib_dir = os.path.join(raw, "calibration")
+        lc = read_fisheycalib(os.path.join(calib_dir, "image_02.yaml"))
+        P0, T = extract_P_from_fisheye_calib(lc), HK.velo_to_cam02(calib_dir)
+        for i in HK.EVAL_FRAMES:
+            velo = read_pc_from_bin(os.path.join(raw, "data_3d_raw", HK.SEQ, "velodyne_points/data", "%010d.bin" % i))
+            u, v, _, _ = HK.gt_points(velo, T, P0, lc)
+            assert ((u >= 0) & (u < HK.W) & (v >= 0) & (v < HK.H)).all(), "fixture: a point with z > 0 leaves the image"
+            assert HK.float_sub2ind_unique(velo, T, P0, lc), "fixture: two points share a float sub2ind value"
+        gt_file = os.path.join(d, "gt.npz")
+        ev = Kitti360FisheyeEvaluator(raw, val, gt_file)
+        for j, (g, m) in enumerate(zip(ev.gt_depths, ev.close_masks)):
+            out["gt%d_idx" % j], out["gt%d_val" % j], out["gt%d_midx" % j] = HK.sparse(g, m)
+            want_g, want_m = HK.ground_truth(read_pc_from_bin(os.path.join(
+                raw, "data_3d_raw", HK.SEQ, "velodyne_points/data", "%010d.bin" % HK.EVAL_FRAMES[j])), T, P0, lc)
+            assert np.array_equal(want_g, g) and np.array_equal(want_m, m), "helper ground truth != reference"
+        # _single_loss on seeded predictions (a smaller map: cv2.resize to the ground truth's size inside, routed to
+        # the single-channel restatement of oracle/eval_oracle.py)
+        from oracle import eval_oracle as EO
+        resize = cv2.resize
+        cv2.resize = lambda src, dsize, interpolation=cv2.INTER_LINEAR: (
+            EO.cv2_resize_linear(src, dsize[0], dsize[1]) if np.ndim(src) == 2 and interpolation == cv2.INTER_LINEAR
+            else resize(src, dsize, interpolation))
+        rng = np.random.RandomState(17)
+        for j in range(len(ev.gt_depths)):
+            pred = (rng.rand(175, 175) * 30 + 0.5).astype(np.float32)
+            r = ev._single_loss(pred.copy(), ev.gt_depths[j], ev.close_masks[j])
+            out["pred%d" % j] = pred
+            out["loss%d" % j] = np.concatenate([[r["ratio"]], r["error"], r["abs_error"]]).astype(np.float64)
+        cv2.resize = resize
+        out["n_gt"] = np.array(len(ev.gt_depths))
+    print("kitti360 fisheye: %d / %d / %d samples, gt hits %s" % (
+        len(out["static_left_index"]), len(out["all_left_index"]), len(out["static_right_index"]),
+        [len(out["gt%d_idx" % j]) for j in range(int(out["n_gt"]))]))
+    np.savez_compressed(os.path.join(GOLD, "kitti360_fisheye.npz"), **out)
+
+
 def gen_loss_options():
     """optional terms of MonoDepth2Decoder.loss no shipped config enables: precomputed motion_mask
     (monodepth2_decoder.py:243-246) and the pose L1 term (:176-183, 322-326), from the REAL decoder"""
@@ -1136,6 +1228,9 @@ if __name__ == "__main__":
     if "--only-options" in sys.argv:
         gen_loss_options()
         sys.exit(0)
+    if "--only-kitti360" in sys.argv:
+        gen_kitti360_fisheye()
+        sys.exit(0)
     if "--only-kitti" in sys.argv:
         gen_kitti_dataset()
         sys.exit(0)
@@ -1152,6 +1247,7 @@ if __name__ == "__main__":
     gen_fisheye()
     gen_model_r50fx()
     gen_kitti_dataset()
+    gen_kitti360_fisheye()
     gen_loss_options()
     gen_teacher_keys()
     gen_sigmoid_decoder()
