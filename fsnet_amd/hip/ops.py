@@ -828,6 +828,50 @@ def lidar_mei_depth(scans, T, mei, H, W, device):
     return op.run()
 
 
+class LidarPinholeDepth:
+    """LiDAR ground truth through a pinhole camera with the KITTI export's duplicate pass, G frames per call
+    (fs_lidar_pinhole_depth; monodepth_utils.py:422-458).  As LidarMeiDepth: buffers are kept between calls of the same
+    (G, H, W), stage() copies the inputs into them, run() issues the kernels only and can be captured into a graph."""
+
+    def __init__(self, G, H, W, device):
+        self.G, self.H, self.W, self.device = G, H, W, torch.device(device)
+        ws = int(lib.fs_lidar_pinhole_depth_workspace_bytes(G, H, W))
+        if ws < 0:
+            raise ValueError("lidar_pinhole_depth: bad shape G=%d H=%d W=%d" % (G, H, W))
+        self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+        self.offsets = torch.zeros(G + 1, dtype=torch.int64, device=self.device)
+        self.P = torch.zeros(G, 12, dtype=torch.float64, device=self.device)
+        self.depth = torch.empty(G, H, W, dtype=torch.float32, device=self.device)
+        self.points = torch.empty(0, 4, dtype=torch.float32, device=self.device)
+
+    def stage(self, scans, P):
+        """scans: G float32 [Ni, 4] arrays / tensors; P: f64 [G, 3, 4] velodyne -> image"""
+        import numpy as np
+        assert len(scans) == self.G
+        counts = [int(s.shape[0]) for s in scans]
+        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        pts = torch.cat([torch.as_tensor(np.asarray(s, dtype=np.float32).reshape(-1, 4)) for s in scans])
+        if self.points.shape[0] != pts.shape[0]:
+            self.points = torch.empty(pts.shape[0], 4, dtype=torch.float32, device=self.device)
+        self.points.copy_(pts)
+        self.offsets.copy_(torch.from_numpy(offs))
+        self.P.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(P, dtype=np.float64).reshape(self.G, 12))))
+
+    def run(self):
+        check(lib.fs_lidar_pinhole_depth(_p(self.points) if self.points.numel() else None, self.offsets.data_ptr(),
+                                         int(self.points.shape[0]), self.P.data_ptr(), self.G, self.H, self.W,
+                                         self.depth.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
+                                         stream_ptr()), "lidar_pinhole_depth")
+        return self.depth
+
+
+def lidar_pinhole_depth(scans, P, H, W, device):
+    """one call: G = len(scans) frames -> depth fp32 [G, H, W] on `device`"""
+    op = LidarPinholeDepth(len(scans), H, W, device)
+    op.stage(scans, P)
+    return op.run()
+
+
 _CENTRE_TABLES = {}
 
 

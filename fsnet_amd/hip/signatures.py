@@ -45,6 +45,9 @@ SIGNATURES = {
     "fs_depth_eval_masked": (C.c_int, [P, P, P, I, I, I, I, I, F, F, I, P, P, P]),
     "fs_lidar_mei_depth": (C.c_int, [P, P, L, P, P, I, I, I, P, P, P, L, P]),
     "fs_lidar_mei_depth_workspace_bytes": (C.c_int64, [I, I, I]),
+    # ABI 15: project_depth_map / generate_depth_map(vel_depth=True) (monodepth_utils.py:368-458)
+    "fs_lidar_pinhole_depth": (C.c_int, [P, P, L, P, I, I, I, P, P, L, P]),
+    "fs_lidar_pinhole_depth_workspace_bytes": (C.c_int64, [I, I, I]),
     "fs_postopt": (C.c_int, [P, P]),
     "fs_postopt_workspace_bytes": (C.c_int64, [I, I, I, I]),
     "fs_optflow_farneback": (C.c_int, [P, P]),

@@ -1,8 +1,8 @@
 """KittiEigenEvaluator with the reference's constructor and methods (monodepth/evaluation/
 kitti_unsupervised_eval.py:11-127).  `_single_loss` runs on the device: resize to the ground truth's size, valid mask
 + Garg crop, median scaling, clamp and the seven depth errors are one HIP launch per image (fs_depth_eval), so a
-validation pass does not copy depth maps to the host.  Ground-truth export from raw velodyne scans (`_precompute`,
-:27-45) is the data layer's job and is not part of this package: the evaluator loads the reference's `gt_saved_file`."""
+validation pass does not copy depth maps to the host.  KittiEigenEvaluator exports its ground truth on the host
+(`_precompute`, :27-45, generate_depth_map); Kitti360Evaluator (:164-212) exports it on the device."""
 import os
 
 import numpy as np
@@ -96,3 +96,69 @@ class KittiEigenEvaluator(object):
         if is_print:
             print(log_str)
         return log_str
+
+
+class Kitti360Evaluator(KittiEigenEvaluator):
+    """KITTI-360 perspective evaluation (reference :164-212): the Eigen metric of the parent, unchanged, on ground truth
+    exported from the raw velodyne scans through image_00's rectified pinhole camera.  `_precompute` reads the split and
+    the image sizes on the host, composes P_velo2img in f64 as the reference does, and projects `group_size` scans per
+    fs_lidar_pinhole_depth call (the reference: project_depth_map per frame, a Python loop over every duplicate index;
+    the host form is monodepth_utils.project_depth_map).  At most `group_size` scans are held in host memory.  The cache
+    is the reference's: `data` float32 [N, H, W] written by np.savez_compressed, an object array when sizes differ."""
+
+    def __init__(self, data_path=None, split_file=None, gt_saved_file=None, is_evaluate_absolute=False, gt_depths=None,
+                 device=None, group_size=8):
+        self.group_size = int(group_size)
+        super().__init__(data_path, split_file, gt_saved_file, is_evaluate_absolute, gt_depths, device)
+
+    def _load_calib(self, calib_dir):
+        from fsnet_amd.monodepth.data.datasets.kitti360_dataset import read_P01_from_sequence, read_T_from_sequence
+        P0, _, R0, _ = read_P01_from_sequence(os.path.join(calib_dir, "perspective.txt"))
+        self.cam_calib = dict(P0=P0, R0=R0,
+                              T_cam2velo=read_T_from_sequence(os.path.join(calib_dir, "calib_cam_to_velo.txt")))
+
+    def velo_to_image(self):
+        """P_velo2img [3, 4] f64, composed exactly as the reference does (:190)"""
+        return self.cam_calib['P0'] @ self.cam_calib['R0'] @ np.linalg.inv(self.cam_calib['T_cam2velo'])
+
+    def _precompute(self, data_path, split_file, gt_saved_file):
+        from PIL import Image
+        from fsnet_amd.monodepth.data.datasets.utils import read_pc_from_bin
+        img_dir = os.path.join(data_path, 'data_2d_raw')
+        pc_dir = os.path.join(data_path, 'data_3d_raw')
+        self._load_calib(os.path.join(data_path, 'calibration'))
+        P = self.velo_to_image()
+        frames = []                       # (scan path, h, w): the scans are read one group at a time below
+        with open(split_file, 'r') as f:
+            for line in f.readlines():
+                sequence_name, _, img_index, _, _ = line.strip().split(',')
+                frame_id = int(img_index)
+                with Image.open(os.path.join(img_dir, sequence_name, 'image_00', 'data_rect',
+                                             "{:010d}.png".format(frame_id))) as im:
+                    w, h = im.size
+                frames.append((os.path.join(pc_dir, sequence_name, "velodyne_points/data",
+                                            "{:010d}.bin".format(frame_id)), h, w))
+        dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        gts = []
+        op, start = None, 0
+        while start < len(frames):
+            h, w = frames[start][1:]
+            stop = start
+            while stop < len(frames) and stop - start < self.group_size and frames[stop][1:] == (h, w):
+                stop += 1
+            G = stop - start
+            if op is None or (op.G, op.H, op.W) != (G, h, w):
+                op = ops.LidarPinholeDepth(G, h, w, dev)
+            op.stage([read_pc_from_bin(fr[0]) for fr in frames[start:stop]], np.stack([P] * G))
+            depth = op.run().cpu().numpy()
+            gts.extend(depth[g] for g in range(G))
+            start = stop
+        if gt_saved_file is not None:
+            if len({g.shape for g in gts}) <= 1:
+                arr = np.array(gts)
+            else:
+                arr = np.empty(len(gts), dtype=object)
+                for k, g in enumerate(gts):
+                    arr[k] = g
+            np.savez_compressed(gt_saved_file, data=arr)
+        self.gt_depths = gts

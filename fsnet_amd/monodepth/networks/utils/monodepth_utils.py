@@ -97,6 +97,21 @@ def generate_depth_map(calib_dir, velo_filename, cam=2, vel_depth=False):
 
     velo = load_velodyne_points(velo_filename)
     velo = velo[velo[:, 0] >= 0, :]                       # in front of the sensor (approximation of "in front of the camera")
+    return _export_depth(velo, P_velo2im, im_shape, vel_depth)
+
+
+def project_depth_map(velo, P_velo2im, im_shape):
+    """scan [N, 4] float32 + 3x4 velodyne -> image matrix -> sparse depth image ([H, W] float64, 0 = no return, the
+    value of a point its velodyne x) — the export of Kitti360Evaluator._precompute (reference monodepth_utils.py:422-458).
+    The device form is fs_lidar_pinhole_depth."""
+    velo = velo[velo[:, 0] >= 0, :].copy()
+    velo[:, 3] = 1.0                                      # homogeneous
+    return _export_depth(velo, P_velo2im, im_shape, True)
+
+
+def _export_depth(velo, P_velo2im, im_shape, vel_depth):
+    """the scatter and duplicate pass generate_depth_map and project_depth_map share; velo: homogeneous, x >= 0"""
+    import numpy as np
     pts = np.dot(P_velo2im, velo.T).T
     pts[:, :2] = pts[:, :2] / pts[:, 2][..., np.newaxis]
     if vel_depth:

@@ -33,7 +33,7 @@ extern "C" {
 
 /* library/ABI version and the ISA the kernels were compiled for ("gfx950").  FS_ABI_VERSION changes whenever an
  * argument struct or a signature below does; a host binding refuses a library that reports another number. */
-#define FS_ABI_VERSION 14
+#define FS_ABI_VERSION 15
 int fs_abi_version(void);
 const char* fs_target_arch(void);
 /* debugging aid: writes the device's constant-rate clock (wall_clock64, 100 MHz) into *slot (u64) on `stream`;
@@ -365,6 +365,21 @@ int fs_lidar_mei_depth(const float* points, const int64_t* offsets, int64_t n_po
                        const double* mei, int G, int H, int W, float* depth, uint8_t* close_mask, void* workspace,
                        int64_t workspace_bytes, void* stream);
 int64_t fs_lidar_mei_depth_workspace_bytes(int G, int H, int W);
+
+/* LiDAR ground truth through a pinhole camera (ABI 15): project_depth_map of Kitti360Evaluator._precompute and the
+ * arithmetic of generate_depth_map(vel_depth=True) (monodepth_utils.py:368-458, sub2ind :291-295).  G frames per call;
+ * points / offsets as in fs_lidar_mei_depth (points 16-byte aligned); P: device f64 [G][12], the 3x4 velodyne -> image
+ * matrix of each frame.  A point counts iff its float32 x >= 0 (no test on the projected z); p = P [x y z 1]^T in f64 in
+ * index order, col = rint(p0 / p2) - 1, row = rint(p1 / p2) - 1 (half to even), kept iff 0 <= col < W, 0 <= row < H.  Its
+ * value is its float32 x (-0.0 is taken as +0.0).  depth [G][H][W] fp32: a pixel takes its last point in scan order; then,
+ * for every group of more than one point sharing the export index row * (W - 1) + col - 1 (one pixel, or the pair
+ * (r, W-1) / (r+1, 0)), the pixel of the group's first point takes the group's minimum; 0 where no point lands.
+ * workspace: at least fs_lidar_pinhole_depth_workspace_bytes(G, H, W) bytes, 16-byte aligned (-1: G, H < 1, W < 2,
+ * G > 65535 or G*H*W >= 2^31).  No host sync: capturable.  Deterministic: the same bits for any run and any grouping
+ * of frames into calls. */
+int fs_lidar_pinhole_depth(const float* points, const int64_t* offsets, int64_t n_points, const double* P, int G, int H,
+                           int W, float* depth, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t fs_lidar_pinhole_depth_workspace_bytes(int G, int H, int W);
 
 /* Sparse-VO depth post-optimisation (postopt_utils.py:8-11, 94-226; KittiEvaluationHook_postopt,
  * base_evaluation_hooks.py:69-127), B images in one fixed launch sequence (capturable: no host sync, the launch count

@@ -774,6 +774,89 @@ def gen_kitti360_fisheye():
     np.savez_compressed(os.path.join(GOLD, "kitti360_fisheye.npz"), **out)
 
 
+def gen_kitti360_persp():
+    """the REAL KITTI360MonoDataset (kitti360_dataset.py:85-220) and Kitti360Evaluator (kitti_unsupervised_eval.py:164-212,
+    project_depth_map with its Counter loop) over the seeded tree of tests/helpers_kitti360_persp.py: the filtered index,
+    relative poses / P2 / camera choice for a fixed seed, the ground-truth maps of _precompute (flat indices + values)
+    and _single_loss on seeded predictions.  Fixture conditions, asserted and printed per frame: at least 1000 pixels
+    hit by two or more points, at least one merged edge pair, and the host mirror (monodepth_utils.project_depth_map of
+    this package) equal to the reference's maps with zero mismatching pixels."""
+    import tempfile
+    import cv2
+    from tests import helpers_kitti360_persp as HP
+    from monodepth.data.datasets.kitti360_dataset import KITTI360MonoDataset
+    from monodepth.evaluation.kitti_unsupervised_eval import Kitti360Evaluator
+    from fsnet_amd.monodepth.networks.utils.monodepth_utils import project_depth_map as host_project
+    mean, std = np.array([0.485, 0.456, 0.406], np.float32), np.array([0.229, 0.224, 0.225], np.float32)
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        raw, train, val = HP.make_tree(d)
+        cases = dict(static_left=dict(is_filter_static=True, use_right_image=False, seed=None),
+                     all_left=dict(is_filter_static=False, use_right_image=False, seed=None),
+                     static_right=dict(is_filter_static=True, use_right_image=True, seed=HP.GOLDEN_DRAW_SEED))
+        for tag, c in cases.items():
+            kw = {k: v for k, v in c.items() if k != "seed"}
+            ds = KITTI360MonoDataset(**HP.dataset_cfg(raw, train, prefix='', **kw))
+            out[tag + "_index"] = np.array([o["img_indexes"] + o["pose_indexes"] for o in ds.imdb], np.int64)
+            if c["seed"] is not None:
+                np.random.seed(c["seed"])
+            cams = []
+            for i in range(len(ds)):
+                smp = ds[i]
+                k = "%s_s%d_" % (tag, i)
+                # which camera the sample came from: the frame the reference normalised, against both PNGs on disk
+                img = npy(smp[("image", 0)])
+                u8 = np.round((img.transpose(1, 2, 0) * std + mean) * 255).astype(np.uint8)
+                from PIL import Image
+                match = [np.array_equal(u8, np.array(Image.open(os.path.join(
+                    raw, "data_2d_raw", HP.SEQ, cam, "data_rect", "%010d.png" % ds.imdb[i]["img_indexes"][0]))))
+                    for cam in ("image_00", "image_01")]
+                assert sum(match) == 1
+                cams.append(match.index(True))
+                out[k + "pose_m"] = np.asarray(smp[("relative_pose", -1)])
+                out[k + "pose_p"] = np.asarray(smp[("relative_pose", 1)])
+                out[k + "P2"], out[k + "original_P2"] = npy(smp["P2"]), np.asarray(smp["original_P2"])
+                pm = smp["patched_mask"]
+                pm = npy(pm) if isinstance(pm, torch.Tensor) else np.asarray(pm)
+                assert pm.shape == (HP.H, HP.W) and (pm == 1).all()
+            out[tag + "_cam"] = np.array(cams, np.int64)
+        gt_file = os.path.join(d, "gt.npz")
+        ev = Kitti360Evaluator(raw, val, gt_file)
+        P = ev.cam_calib['P0'] @ ev.cam_calib['R0'] @ np.linalg.inv(ev.cam_calib['T_cam2velo'])
+        assert np.array_equal(P, HP.velo_to_image(raw))
+        counts = []
+        for j, g in enumerate(ev.gt_depths):
+            scan = HP.scan(raw, HP.EVAL_FRAMES[j])
+            dup, pairs = HP.fixture_counts(scan, P)
+            mine = host_project(scan, P, np.array([HP.H, HP.W])).astype(np.float32)
+            bad = int((mine != g).sum())
+            counts.append((dup, pairs, bad))
+            assert g.dtype == np.float32 and g.shape == (HP.H, HP.W)
+            assert dup >= 1000 and pairs >= 1 and bad == 0, (j, dup, pairs, bad)
+            out["gt%d_idx" % j], out["gt%d_val" % j] = HP.sparse(g)
+            assert np.array_equal(HP.dense(out["gt%d_idx" % j], out["gt%d_val" % j]), g)
+        from oracle import eval_oracle as EO
+        resize = cv2.resize
+        cv2.resize = lambda src, dsize, interpolation=cv2.INTER_LINEAR: (
+            EO.cv2_resize_linear(src, dsize[0], dsize[1]) if np.ndim(src) == 2 and interpolation == cv2.INTER_LINEAR
+            else resize(src, dsize, interpolation))
+        rng = np.random.RandomState(19)
+        for j in range(len(ev.gt_depths)):
+            pred = (rng.rand(47, 155) * 30 + 0.5).astype(np.float32)
+            r = ev._single_loss(pred.copy(), ev.gt_depths[j])
+            out["pred%d" % j] = pred
+            out["loss%d" % j] = np.concatenate([[r["ratio"]], r["error"], r["abs_error"]]).astype(np.float64)
+        cv2.resize = resize
+        out["n_gt"] = np.array(len(ev.gt_depths))
+    print("kitti360 perspective: %d / %d / %d samples, cameras %s" % (
+        len(out["static_left_index"]), len(out["all_left_index"]), len(out["static_right_index"]),
+        out["static_right_cam"].tolist()))
+    for j, (dup, pairs, bad) in enumerate(counts):
+        print("  frame %d: %d pixels hit twice or more, %d merged edge pairs, %d pixels where the host mirror differs "
+              "from the reference, %d pixels hit" % (j, dup, pairs, bad, len(out["gt%d_idx" % j])))
+    np.savez_compressed(os.path.join(GOLD, "kitti360_persp.npz"), **out)
+
+
 def gen_loss_options():
     """optional terms of MonoDepth2Decoder.loss no shipped config enables: precomputed motion_mask
     (monodepth2_decoder.py:243-246) and the pose L1 term (:176-183, 322-326), from the REAL decoder"""
@@ -1231,6 +1314,9 @@ if __name__ == "__main__":
     if "--only-kitti360" in sys.argv:
         gen_kitti360_fisheye()
         sys.exit(0)
+    if "--only-kitti360-persp" in sys.argv:
+        gen_kitti360_persp()
+        sys.exit(0)
     if "--only-kitti" in sys.argv:
         gen_kitti_dataset()
         sys.exit(0)
@@ -1248,6 +1334,7 @@ if __name__ == "__main__":
     gen_model_r50fx()
     gen_kitti_dataset()
     gen_kitti360_fisheye()
+    gen_kitti360_persp()
     gen_loss_options()
     gen_teacher_keys()
     gen_sigmoid_decoder()
