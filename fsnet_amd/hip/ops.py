@@ -781,26 +781,23 @@ def depth_eval_masked(pred, gt, mask=None, lo=0.3, hi=60.0, crop=False):
     return out
 
 
-class LidarMeiDepth:
-    """LiDAR ground truth through the Mei fisheye model, G frames per call (fs_lidar_mei_depth;
-    kitti360_fisheye_eval.py:97-145).  Buffers are kept between calls of the same (G, H, W) so that a call can be
-    captured into a graph and replayed: stage() copies the inputs into them, run() issues the kernels only."""
+class _LidarDepth:
+    """What the LiDAR ground-truth ops share: the workspace, the scans of G frames as one `points` [N, 4] with
+    `offsets` [G + 1] into it, and the `depth` maps.  Buffers are kept between calls of the same (G, H, W) so that a
+    call can be captured into a graph and replayed: stage() copies the inputs into them, run() issues the kernels only."""
 
-    def __init__(self, G, H, W, device):
+    def __init__(self, name, workspace_bytes, G, H, W, device):
         self.G, self.H, self.W, self.device = G, H, W, torch.device(device)
-        ws = int(lib.fs_lidar_mei_depth_workspace_bytes(G, H, W))
+        ws = int(workspace_bytes(G, H, W))
         if ws < 0:
-            raise ValueError("lidar_mei_depth: bad shape G=%d H=%d W=%d" % (G, H, W))
+            raise ValueError("%s: bad shape G=%d H=%d W=%d" % (name, G, H, W))
         self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
         self.offsets = torch.zeros(G + 1, dtype=torch.int64, device=self.device)
-        self.T = torch.zeros(G, 16, dtype=torch.float64, device=self.device)
-        self.mei = torch.zeros(G, 7, dtype=torch.float64, device=self.device)
         self.depth = torch.empty(G, H, W, dtype=torch.float32, device=self.device)
-        self.close_mask = torch.empty(G, H, W, dtype=torch.uint8, device=self.device)
         self.points = torch.empty(0, 4, dtype=torch.float32, device=self.device)
 
-    def stage(self, scans, T, mei):
-        """scans: G float32 [Ni, 4] arrays / tensors; T: f64 [G, 4, 4]; mei: f64 [G, 7] = gamma1 gamma2 u0 v0 k1 k2 xi"""
+    def _stage_scans(self, scans):
+        """scans: G float32 [Ni, 4] arrays / tensors"""
         import numpy as np
         assert len(scans) == self.G
         counts = [int(s.shape[0]) for s in scans]
@@ -810,11 +807,34 @@ class LidarMeiDepth:
             self.points = torch.empty(pts.shape[0], 4, dtype=torch.float32, device=self.device)
         self.points.copy_(pts)
         self.offsets.copy_(torch.from_numpy(offs))
-        self.T.copy_(torch.from_numpy(np.asarray(T, dtype=np.float64).reshape(self.G, 16)))
-        self.mei.copy_(torch.from_numpy(np.asarray(mei, dtype=np.float64).reshape(self.G, 7)))
+
+    def _stage_f64(self, dst, src):
+        import numpy as np
+        dst.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(src, dtype=np.float64).reshape(dst.shape))))
+
+    def _points_ptr(self):
+        """NULL for an empty cloud"""
+        return _p(self.points) if self.points.numel() else None
+
+
+class LidarMeiDepth(_LidarDepth):
+    """LiDAR ground truth through the Mei fisheye model, G frames per call (fs_lidar_mei_depth;
+    kitti360_fisheye_eval.py:97-145)."""
+
+    def __init__(self, G, H, W, device):
+        super().__init__("lidar_mei_depth", lib.fs_lidar_mei_depth_workspace_bytes, G, H, W, device)
+        self.T = torch.zeros(G, 16, dtype=torch.float64, device=self.device)
+        self.mei = torch.zeros(G, 7, dtype=torch.float64, device=self.device)
+        self.close_mask = torch.empty(G, H, W, dtype=torch.uint8, device=self.device)
+
+    def stage(self, scans, T, mei):
+        """scans: G float32 [Ni, 4] arrays / tensors; T: f64 [G, 4, 4]; mei: f64 [G, 7] = gamma1 gamma2 u0 v0 k1 k2 xi"""
+        self._stage_scans(scans)
+        self._stage_f64(self.T, T)
+        self._stage_f64(self.mei, mei)
 
     def run(self):
-        check(lib.fs_lidar_mei_depth(_p(self.points) if self.points.numel() else None, self.offsets.data_ptr(),
+        check(lib.fs_lidar_mei_depth(self._points_ptr(), self.offsets.data_ptr(),
                                      int(self.points.shape[0]), self.T.data_ptr(), self.mei.data_ptr(), self.G, self.H,
                                      self.W, self.depth.data_ptr(), self.close_mask.data_ptr(),
                                      self.workspace.data_ptr(), self.workspace.numel(), stream_ptr()), "lidar_mei_depth")
@@ -828,37 +848,21 @@ def lidar_mei_depth(scans, T, mei, H, W, device):
     return op.run()
 
 
-class LidarPinholeDepth:
+class LidarPinholeDepth(_LidarDepth):
     """LiDAR ground truth through a pinhole camera with the KITTI export's duplicate pass, G frames per call
-    (fs_lidar_pinhole_depth; monodepth_utils.py:422-458).  As LidarMeiDepth: buffers are kept between calls of the same
-    (G, H, W), stage() copies the inputs into them, run() issues the kernels only and can be captured into a graph."""
+    (fs_lidar_pinhole_depth; monodepth_utils.py:422-458)."""
 
     def __init__(self, G, H, W, device):
-        self.G, self.H, self.W, self.device = G, H, W, torch.device(device)
-        ws = int(lib.fs_lidar_pinhole_depth_workspace_bytes(G, H, W))
-        if ws < 0:
-            raise ValueError("lidar_pinhole_depth: bad shape G=%d H=%d W=%d" % (G, H, W))
-        self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
-        self.offsets = torch.zeros(G + 1, dtype=torch.int64, device=self.device)
+        super().__init__("lidar_pinhole_depth", lib.fs_lidar_pinhole_depth_workspace_bytes, G, H, W, device)
         self.P = torch.zeros(G, 12, dtype=torch.float64, device=self.device)
-        self.depth = torch.empty(G, H, W, dtype=torch.float32, device=self.device)
-        self.points = torch.empty(0, 4, dtype=torch.float32, device=self.device)
 
     def stage(self, scans, P):
         """scans: G float32 [Ni, 4] arrays / tensors; P: f64 [G, 3, 4] velodyne -> image"""
-        import numpy as np
-        assert len(scans) == self.G
-        counts = [int(s.shape[0]) for s in scans]
-        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        pts = torch.cat([torch.as_tensor(np.asarray(s, dtype=np.float32).reshape(-1, 4)) for s in scans])
-        if self.points.shape[0] != pts.shape[0]:
-            self.points = torch.empty(pts.shape[0], 4, dtype=torch.float32, device=self.device)
-        self.points.copy_(pts)
-        self.offsets.copy_(torch.from_numpy(offs))
-        self.P.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(P, dtype=np.float64).reshape(self.G, 12))))
+        self._stage_scans(scans)
+        self._stage_f64(self.P, P)
 
     def run(self):
-        check(lib.fs_lidar_pinhole_depth(_p(self.points) if self.points.numel() else None, self.offsets.data_ptr(),
+        check(lib.fs_lidar_pinhole_depth(self._points_ptr(), self.offsets.data_ptr(),
                                          int(self.points.shape[0]), self.P.data_ptr(), self.G, self.H, self.W,
                                          self.depth.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
                                          stream_ptr()), "lidar_pinhole_depth")

@@ -1,5 +1,6 @@
 """KITTI-360 fisheye triplet dataset with the reference's module path, class name, constructor keys and sample contract
-(monodepth/data/datasets/fisheye_dataset.py:1-262): comma-separated split "sequence, pose index, image index, former,
+(monodepth/data/datasets/fisheye_dataset.py:1-262), on the base it shares with the perspective dataset
+(kitti360_triplet.KITTI360TripletDataset): comma-separated split "sequence, pose index, image index, former,
 latter" -> image / pose index triplets, the Mei calibration of both fisheye cameras (image_02.yaml / image_03.yaml),
 camera-to-pose extrinsics, data_poses -> ('relative_pose', f), raw uint8 frames under ('image', f), P2 / original_P2 /
 calib_meta of the camera drawn for the sample and a float64 patched_mask — then the configured augmentation.  With the
@@ -15,22 +16,9 @@ import os
 from copy import deepcopy
 
 import numpy as np
-import torch.utils.data
 
-from fsnet_amd.monodepth.data.datasets.utils import cam_relative_pose_nusc, read_image
-from fsnet_amd.vision_base.utils.builder import build
-from fsnet_amd.vision_base.utils.utils import EasyDict
-
-
-def _read_camera_lines(file, keys):
-    out = {k: np.eye(4) for k in keys}
-    with open(file, 'r') as f:
-        for line in f.readlines():
-            for k in keys:
-                if line.startswith(k):
-                    data = line.strip().split(" ")
-                    out[k][0:3, :] = np.reshape(np.array([float(x) for x in data[1:13]]), [3, 4])
-    return out
+from fsnet_amd.monodepth.data.datasets.kitti360_triplet import (  # noqa: F401  (the readers keep their names here)
+    KITTI360TripletDataset, _read_camera_lines, read_cam2velo_from_sequence, read_poses_file)
 
 
 def read_extrinsic_from_sequence(file):
@@ -60,19 +48,6 @@ def extract_P_from_fisheye_calib(calib):
     return P
 
 
-def read_poses_file(file):
-    """data_poses/<seq>/poses.txt: "frame r00 ... t2" per line -> (key frames, f64 [N, 4, 4]) (reference :60-71)"""
-    key_frames, poses = [], []
-    with open(file, 'r') as f:
-        for line in f.readlines():
-            data = line.strip().split(" ")
-            key_frames.append(int(data[0]))
-            pose = np.eye(4)
-            pose[0:3, :] = np.array([float(x) for x in data[1:13]]).reshape([3, 4])
-            poses.append(pose)
-    return key_frames, np.array(poses)
-
-
 def read_split_file(file):
     """KITTI-style split "folder index side" (reference :74-93)"""
     imdb = []
@@ -84,83 +59,20 @@ def read_split_file(file):
     return imdb
 
 
-def read_cam2velo_from_sequence(file):
-    """calib_cam_to_velo.txt: 12 numbers on the first line -> 4x4 (reference :95-105)"""
-    with open(file, 'r') as f:
-        line = f.readlines()[0]
-        data = line.strip().split(" ")
-        T = np.array([float(x) for x in data[0:12]]).reshape([3, 4])
-    T_cam2velo = np.eye(4)
-    T_cam2velo[0:3, :] = T
-    return T_cam2velo
+class KITTI360FisheyeDataset(KITTI360TripletDataset):
+    camera_dirs = ('image_02', 'image_03')
+    image_subdir = 'data_rgb'
 
-
-class KITTI360FisheyeDataset(torch.utils.data.Dataset):
     def __init__(self, **data_cfg):
-        data_cfg = EasyDict(data_cfg)
-        super().__init__()
-        self.raw_path = getattr(data_cfg, 'raw_path', '/data/KITTI-360')
-        self.meta_file = getattr(data_cfg, 'split_file', 'kitti360_meta.txt')
+        super().__init__(**data_cfg)
+        fish_eye_mask = data_cfg.get('fisheye_mask', None)
+        self.fish_eye_mask = None if fish_eye_mask is None else np.array(_read_mask(fish_eye_mask))
+
+    def _data_dirs(self, data_cfg):
         self.resized_root = getattr(data_cfg, 'resized_root', None)
         if self.resized_root is not None:
-            self.img_dir = self.resized_root
-            self.calib_dir = os.path.join(self.resized_root, 'calibration')
-        else:
-            self.img_dir = os.path.join(self.raw_path, 'data_2d_raw')
-            self.calib_dir = os.path.join(self.raw_path, 'calibration')
-        self.pose_dir = os.path.join(self.raw_path, 'data_poses')
-        self.pc_dir = os.path.join(self.raw_path, 'data_3d_raw')
-
-        self.frame_ids = list(getattr(data_cfg, 'frame_ids', [0, -1, 1]))
-        self.imdb = []
-        self.sequence_names = set()
-        with open(self.meta_file, 'r') as f:
-            for line in f.readlines():
-                sequence_name, pose_index, img_index, former_index, latter_index = line.strip().split(',')
-                pose_index, img_index = int(pose_index), int(img_index)
-                index_dict = {0: img_index, -1: int(former_index), 1: int(latter_index)}
-                self.sequence_names.add(sequence_name)
-                self.imdb.append(dict(sequence_name=sequence_name,
-                                      pose_indexes=[pose_index + ind for ind in self.frame_ids],
-                                      img_indexes=[index_dict[ind] for ind in self.frame_ids]))
-        self._load_calib()
-        self._load_keypose()
-
-        self.is_motion_mask = getattr(data_cfg, 'is_motion_mask', False)      # accepted, unused (as in the reference)
-        if self.is_motion_mask:
-            self.precompute_path = getattr(data_cfg, 'motion_mask_path', "")
-
-        self.is_filter_static = getattr(data_cfg, 'is_filter_static', True)
-        self.filter_threshold = getattr(data_cfg, 'filter_threshold', 0.03)
-        if self.is_filter_static:
-            self.imdb = self._filter_indexes()
-
-        self.use_right_image = getattr(data_cfg, 'use_right_image', True)
-
-        fish_eye_mask = getattr(data_cfg, 'fisheye_mask', None)
-        self.fish_eye_mask = None if fish_eye_mask is None else np.array(_read_mask(fish_eye_mask))
-        self.transform = build(**data_cfg.augmentation)
-
-    def _relative_pose(self, poses, i, extrinsics):
-        return cam_relative_pose_nusc(poses[0], poses[i + 1], np.linalg.inv(extrinsics)).astype(np.float32)
-
-    def _filter_indexes(self):
-        """drop samples that moved less than filter_threshold or more than 3 m to a neighbour frame (reference
-        :169-190; always measured with the left camera's extrinsics)"""
-        imdb = []
-        print(f"Start Filtering indexes, original length {len(self)}")
-        extrinsics = self.cam_calib['T_rect02baselink']
-        for obj in self.imdb:
-            poses = self.keypose[obj['sequence_name']][obj['pose_indexes']]
-            is_overlook = False
-            for i, _ in enumerate(self.frame_ids[1:]):
-                translation = np.linalg.norm(self._relative_pose(poses, i, extrinsics)[0:3, 3])
-                if translation < self.filter_threshold or translation > 3:
-                    is_overlook = True
-            if not is_overlook:
-                imdb.append(obj)
-        print(f"Finished filtering indexes, find dynamic instances {len(imdb)}")
-        return imdb
+            return self.resized_root, os.path.join(self.resized_root, 'calibration')
+        return super()._data_dirs(data_cfg)
 
     def _load_calib(self):
         left_calib = read_fisheycalib(os.path.join(self.calib_dir, "image_02.yaml"))
@@ -171,48 +83,19 @@ class KITTI360FisheyeDataset(torch.utils.data.Dataset):
                               T_rect12baselink=T_image2pose_dict['T_image3'],
                               left_meta=left_calib, right_meta=right_calib)
 
-    def _load_keypose(self):
-        self.keypose = {}
-        for sequence_name in self.sequence_names:
-            _, poses = read_poses_file(os.path.join(self.pose_dir, sequence_name, 'poses.txt'))
-            self.keypose[sequence_name] = poses
-
-    def __len__(self):
-        return len(self.imdb)
-
-    def __getitem__(self, index):
-        obj = self.imdb[index]
-        sequence_name, pose_indexes, img_indexes = obj['sequence_name'], obj['pose_indexes'], obj['img_indexes']
-        if (not self.use_right_image) or (np.random.rand() < 0.5):
-            extrinsics, image_dir_name = self.cam_calib['T_rect02baselink'], 'image_02'
-            P2, calib_meta = self.cam_calib['P0'], self.cam_calib['left_meta']
-        else:
-            extrinsics, image_dir_name = self.cam_calib['T_rect12baselink'], 'image_03'
-            P2, calib_meta = self.cam_calib['P1'], self.cam_calib['right_meta']
-
-        data = dict()
-        poses = self.keypose[sequence_name][pose_indexes]
-        for i, idx in enumerate(self.frame_ids[1:]):
-            data[('relative_pose', idx)] = self._relative_pose(poses, i, extrinsics)
-        image_dir = os.path.join(self.img_dir, sequence_name, image_dir_name, 'data_rgb')
-        for frame_id, i in zip(self.frame_ids, img_indexes):
-            data[('image', frame_id)] = read_image(os.path.join(image_dir, f"{i:010d}.png"))
-
-        data['P2'] = np.zeros((3, 4), dtype=np.float32)
-        data['P2'][0:3, 0:3] = P2[0:3, 0:3]
-        data['original_P2'] = data['P2'].copy()
-        data['calib_meta'] = deepcopy(calib_meta)
-
-        h, w, _ = data[("image", 0)].shape
+    def _sample(self, index):
+        data, right = super()._sample(index)
+        mask = data.pop("patched_mask")                 # calib_meta comes before it in the reference's sample
+        data['calib_meta'] = deepcopy(self.cam_calib['right_meta' if right else 'left_meta'])
         if self.fish_eye_mask is not None:
-            m = self.fish_eye_mask
-            if m.shape[:2] != (h, w):
+            h, w = mask.shape
+            mask = self.fish_eye_mask
+            if mask.shape[:2] != (h, w):
                 from fsnet_amd.monodepth.networks.utils.postopt_utils import resize_nearest
-                m = resize_nearest(m, w, h)
-            data["patched_mask"] = np.asarray(m, dtype=np.float64)
-        else:
-            data["patched_mask"] = np.ones([h, w])
-        return self.transform(deepcopy(data))
+                mask = resize_nearest(mask, w, h)
+            mask = np.asarray(mask, dtype=np.float64)
+        data["patched_mask"] = mask
+        return data, right
 
 
 def _read_mask(path):

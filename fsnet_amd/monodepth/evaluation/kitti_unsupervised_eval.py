@@ -2,13 +2,27 @@
 kitti_unsupervised_eval.py:11-127).  `_single_loss` runs on the device: resize to the ground truth's size, valid mask
 + Garg crop, median scaling, clamp and the seven depth errors are one HIP launch per image (fs_depth_eval), so a
 validation pass does not copy depth maps to the host.  KittiEigenEvaluator exports its ground truth on the host
-(`_precompute`, :27-45, generate_depth_map); Kitti360Evaluator (:164-212) exports it on the device."""
+(`_precompute`, :27-45, generate_depth_map); Kitti360Evaluator (:164-212) exports it on the device, with the loop
+(Kitti360LidarExport) that Kitti360FisheyeEvaluator's export runs too."""
 import os
 
 import numpy as np
 import torch
 
 from fsnet_amd.hip import ops
+
+
+def stack_maps(maps):
+    """maps of one size as one array [N, H, W]; of several sizes (the Eigen split mixes recording dates whose rectified
+    image sizes differ: 375x1242, 370x1224, 376x1241 ...) as an object array, which a ragged list only becomes when
+    asked (the reference's np.array(gts) relied on an older NumPy doing that implicitly; NumPy >= 1.24 raises).  The
+    evaluators load their caches with allow_pickle=True."""
+    if len({m.shape for m in maps}) <= 1:
+        return np.array(maps)
+    arr = np.empty(len(maps), dtype=object)
+    for k, m in enumerate(maps):
+        arr[k] = m
+    return arr
 
 
 class KittiEigenEvaluator(object):
@@ -39,18 +53,15 @@ class KittiEigenEvaluator(object):
                 folder, frame_id, _ = line.split()
                 scan = os.path.join(data_path, folder, "velodyne_points/data", "{:010d}.bin".format(int(frame_id)))
                 gts.append(generate_depth_map(os.path.join(data_path, folder.split("/")[0]), scan, 2, True).astype(np.float32))
-        # the Eigen split mixes recording dates whose rectified image sizes differ (375x1242, 370x1224, 376x1241 ...):
-        # a ragged list only becomes an array as dtype=object (the reference's np.array(gts) relied on an older NumPy
-        # doing that implicitly; NumPy >= 1.24 raises).  The loader above passes allow_pickle=True.
         if gt_saved_file is not None:
-            if len({g.shape for g in gts}) <= 1:
-                arr = np.array(gts)
-            else:
-                arr = np.empty(len(gts), dtype=object)
-                for k, g in enumerate(gts):
-                    arr[k] = g
-            np.savez_compressed(gt_saved_file, data=arr)
+            np.savez_compressed(gt_saved_file, data=stack_maps(gts))
         self.gt_depths = gts
+
+    def _device_for(self, depth_0=None):
+        """the device of the prediction, else the configured one, else the current one"""
+        if isinstance(depth_0, torch.Tensor) and depth_0.is_cuda:
+            return depth_0.device
+        return self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
 
     def _gt(self, index, device):
         g = self._gt_dev.get(index)
@@ -62,11 +73,7 @@ class KittiEigenEvaluator(object):
 
     def _single_loss(self, depth_0, gt_depth):
         """depth_0: predicted depth [h, w] (device tensor, or numpy as in the reference); gt_depth: [H, W]."""
-        dev = self.device
-        if isinstance(depth_0, torch.Tensor) and depth_0.is_cuda:
-            dev = depth_0.device
-        if dev is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = self._device_for(depth_0)
         pred = torch.as_tensor(depth_0, dtype=torch.float32).to(dev)
         gt = torch.as_tensor(gt_depth, dtype=torch.float32).to(dev)
         out = ops.depth_eval(pred[None], gt[None])[0].cpu().numpy()
@@ -75,9 +82,7 @@ class KittiEigenEvaluator(object):
         return dict(ratio=np.float32(out[0]), error=tuple(out[1:8]), abs_error=tuple(out[8:15]))
 
     def single_call(self, depth_0, index):
-        dev = depth_0.device if isinstance(depth_0, torch.Tensor) and depth_0.is_cuda else (
-            self.device or torch.device("cuda", torch.cuda.current_device()))
-        return self._single_loss(depth_0, self._gt(index, dev))
+        return self._single_loss(depth_0, self._gt(index, self._device_for(depth_0)))
 
     def device_errors(self, depth_0, index):
         """f64 [16] on the device: ratio, err[7], abs_err[7], n_valid of frame `index` (fs_depth_eval) — what the
@@ -98,7 +103,48 @@ class KittiEigenEvaluator(object):
         return log_str
 
 
-class Kitti360Evaluator(KittiEigenEvaluator):
+class Kitti360LidarExport(object):
+    """The ground-truth export loop of the KITTI-360 evaluators, which set `group_size`: at most that many scans are
+    held in host memory and projected per call of a LiDAR op."""
+
+    def _export_lidar(self, data_path, split_file, camera, image_subdir, op_cls, *frame_args):
+        """Reads the comma-separated split and, for its size, each frame of `camera`/`image_subdir`; groups up to
+        `group_size` consecutive frames of equal size; per group reads the scans, stages them and `frame_args` (the
+        same for every frame) in an `op_cls(G, H, W, device)` (kept while (G, H, W) stays) and runs it.  Returns, per
+        frame, the tuple of host arrays the op puts out."""
+        from PIL import Image
+        from fsnet_amd.monodepth.data.datasets.utils import read_pc_from_bin
+        img_dir = os.path.join(data_path, 'data_2d_raw')
+        pc_dir = os.path.join(data_path, 'data_3d_raw')
+        frames = []                       # (scan path, h, w): the scans are read one group at a time below
+        with open(split_file, 'r') as f:
+            for line in f.readlines():
+                sequence_name, _, img_index, _, _ = line.strip().split(',')
+                frame_id = int(img_index)
+                with Image.open(os.path.join(img_dir, sequence_name, camera, image_subdir,
+                                             "{:010d}.png".format(frame_id))) as im:
+                    w, h = im.size
+                frames.append((os.path.join(pc_dir, sequence_name, "velodyne_points/data",
+                                            "{:010d}.bin".format(frame_id)), h, w))
+        dev = self._device_for()
+        maps = []
+        op, start = None, 0
+        while start < len(frames):
+            h, w = frames[start][1:]
+            stop = start
+            while stop < len(frames) and stop - start < self.group_size and frames[stop][1:] == (h, w):
+                stop += 1
+            G = stop - start
+            if op is None or (op.G, op.H, op.W) != (G, h, w):
+                op = op_cls(G, h, w, dev)
+            op.stage([read_pc_from_bin(fr[0]) for fr in frames[start:stop]], *[np.stack([a] * G) for a in frame_args])
+            out = op.run()
+            maps.extend(zip(*[o.cpu().numpy() for o in (out if isinstance(out, tuple) else (out,))]))
+            start = stop
+        return maps
+
+
+class Kitti360Evaluator(Kitti360LidarExport, KittiEigenEvaluator):
     """KITTI-360 perspective evaluation (reference :164-212): the Eigen metric of the parent, unchanged, on ground truth
     exported from the raw velodyne scans through image_00's rectified pinhole camera.  `_precompute` reads the split and
     the image sizes on the host, composes P_velo2img in f64 as the reference does, and projects `group_size` scans per
@@ -122,43 +168,9 @@ class Kitti360Evaluator(KittiEigenEvaluator):
         return self.cam_calib['P0'] @ self.cam_calib['R0'] @ np.linalg.inv(self.cam_calib['T_cam2velo'])
 
     def _precompute(self, data_path, split_file, gt_saved_file):
-        from PIL import Image
-        from fsnet_amd.monodepth.data.datasets.utils import read_pc_from_bin
-        img_dir = os.path.join(data_path, 'data_2d_raw')
-        pc_dir = os.path.join(data_path, 'data_3d_raw')
         self._load_calib(os.path.join(data_path, 'calibration'))
-        P = self.velo_to_image()
-        frames = []                       # (scan path, h, w): the scans are read one group at a time below
-        with open(split_file, 'r') as f:
-            for line in f.readlines():
-                sequence_name, _, img_index, _, _ = line.strip().split(',')
-                frame_id = int(img_index)
-                with Image.open(os.path.join(img_dir, sequence_name, 'image_00', 'data_rect',
-                                             "{:010d}.png".format(frame_id))) as im:
-                    w, h = im.size
-                frames.append((os.path.join(pc_dir, sequence_name, "velodyne_points/data",
-                                            "{:010d}.bin".format(frame_id)), h, w))
-        dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
-        gts = []
-        op, start = None, 0
-        while start < len(frames):
-            h, w = frames[start][1:]
-            stop = start
-            while stop < len(frames) and stop - start < self.group_size and frames[stop][1:] == (h, w):
-                stop += 1
-            G = stop - start
-            if op is None or (op.G, op.H, op.W) != (G, h, w):
-                op = ops.LidarPinholeDepth(G, h, w, dev)
-            op.stage([read_pc_from_bin(fr[0]) for fr in frames[start:stop]], np.stack([P] * G))
-            depth = op.run().cpu().numpy()
-            gts.extend(depth[g] for g in range(G))
-            start = stop
+        gts = [depth for depth, in self._export_lidar(data_path, split_file, 'image_00', 'data_rect',
+                                                      ops.LidarPinholeDepth, self.velo_to_image())]
         if gt_saved_file is not None:
-            if len({g.shape for g in gts}) <= 1:
-                arr = np.array(gts)
-            else:
-                arr = np.empty(len(gts), dtype=object)
-                for k, g in enumerate(gts):
-                    arr[k] = g
-            np.savez_compressed(gt_saved_file, data=arr)
+            np.savez_compressed(gt_saved_file, data=stack_maps(gts))
         self.gt_depths = gts

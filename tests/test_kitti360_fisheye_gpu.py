@@ -83,21 +83,7 @@ def test_ground_truth_deterministic_and_capturable(dev, tree):
     m3 = torch.cat([o[1] for o in threes])
     op = ops.LidarMeiDepth(G, HK.H, HK.W, dev)
     op.stage(scans, Ts, meis)
-    op.run()
-    torch.cuda.synchronize()
-    op.depth.fill_(-1.0)
-    op.close_mask.fill_(7)
-    graph = torch.cuda.CUDAGraph()
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        with torch.cuda.graph(graph, stream=s):
-            op.run()
-    torch.cuda.current_stream().wait_stream(s)
-    op.depth.fill_(-1.0)
-    op.close_mask.fill_(7)
-    graph.replay()
-    torch.cuda.synchronize()
+    HK.run_captured(op, dict(depth=-1.0, close_mask=7))
     for d, m in ((b[0], b[1]), (d1, m1), (d3, m3), (op.depth, op.close_mask)):
         assert torch.equal(d.view(torch.int32), a[0].view(torch.int32)) and torch.equal(m, a[1])
 
@@ -111,15 +97,6 @@ def _cases(rng, H, W, h, w):
     return pred, gt, close
 
 
-def _check(got, want, n_valid):
-    assert abs(float(got["ratio"]) - float(want["ratio"])) <= 1e-5 * abs(float(want["ratio"]))
-    for key in ("error", "abs_error"):
-        a, b = np.array(got[key], np.float64), np.array(want[key], np.float64)
-        print(key, np.abs(a - b).max())
-        assert np.abs(a[:4] - b[:4]).max() <= 2e-5 * max(1.0, np.abs(b[:4]).max()), (key, a, b)
-        assert np.abs(a[4:] - b[4:]).max() <= 3.0 / max(1, n_valid // 4), (key, a, b)
-
-
 def test_masked_metric_matches_reference_and_restatement(dev):
     from oracle import eval_oracle as EO
     from fsnet_amd.monodepth.evaluation.kitti360_fisheye_eval import Kitti360FisheyeEvaluator
@@ -131,7 +108,7 @@ def test_masked_metric_matches_reference_and_restatement(dev):
         want = g["loss%d" % j]
         got = ev.single_call(torch.from_numpy(g["pred%d" % j]).to(dev), j)
         nv = int(((gts[j] > np.float32(0.3)) & (gts[j] < np.float32(60)) & masks[j]).sum())
-        _check(got, dict(ratio=want[0], error=want[1:8], abs_error=want[8:15]), nv)
+        HK.check_metric(got, dict(ratio=want[0], error=want[1:8], abs_error=want[8:15]), nv)
         row = ev.device_errors(torch.from_numpy(g["pred%d" % j]).to(dev), j).cpu().numpy()
         assert int(row[15]) == nv
     rng = np.random.RandomState(23)
@@ -139,14 +116,14 @@ def test_masked_metric_matches_reference_and_restatement(dev):
         pred, gt, close = _cases(rng, H, W, h, w)
         want = HK.single_loss(EO.cv2_resize_linear(pred, W, H), gt, close)
         got = ev._single_loss(torch.from_numpy(pred).to(dev), gt, close)
-        _check(got, want, int(((gt > np.float32(0.3)) & (gt < np.float32(60)) & close).sum()))
+        HK.check_metric(got, want, int(((gt > np.float32(0.3)) & (gt < np.float32(60)) & close).sum()))
     # negative predictions (a fisheye depth is Z x norm, negative where the ray table is invalid): np.median orders
     # them below the positive ones
     pred, gt, close = _cases(rng, 120, 200, 120, 200)
     pred[rng.rand(120, 200) < 0.45] *= -1.0
     want = HK.single_loss(pred, gt, close)
     got = ev._single_loss(torch.from_numpy(pred).to(dev), gt, close)
-    _check(got, want, int(((gt > np.float32(0.3)) & (gt < np.float32(60)) & close).sum()))
+    HK.check_metric(got, want, int(((gt > np.float32(0.3)) & (gt < np.float32(60)) & close).sum()))
     # the crop flag and the mask-less form of fs_depth_eval_masked, against the same restatement
     from fsnet_amd.hip import ops
     for crop, with_mask in ((True, True), (False, False), (True, False)):
@@ -165,7 +142,7 @@ def test_masked_metric_matches_reference_and_restatement(dev):
                                     torch.from_numpy(close).to(dev)[None] if with_mask else None, crop=crop)[0]
         row = row.cpu().numpy()
         assert int(row[15]) == int(valid.sum()), (crop, with_mask)
-        _check(dict(ratio=row[0], error=row[1:8], abs_error=row[8:15]), want, int(valid.sum()))
+        HK.check_metric(dict(ratio=row[0], error=row[1:8], abs_error=row[8:15]), want, int(valid.sum()))
     with pytest.raises(ValueError):
         ev._single_loss(torch.ones(50, 60, device=dev), np.full((50, 60), 70.0, np.float32), np.ones((50, 60), bool))
     with pytest.raises(ValueError):
@@ -196,9 +173,6 @@ def test_evaluator_round_trip(dev, tree, tmp_path):
             assert np.allclose(a[key], b[key], rtol=1e-12, atol=0)
 
 
-MEAN, STD = np.array([0.485, 0.456, 0.406]), np.array([0.229, 0.224, 0.225])
-
-
 def _fisheye_model(h, w, dev):
     """configs[3]'s meta-arch (MonoDepthWPose + FishEyeDecoder, ResNet-18, 64 bins, max depth 150) at h x w, fp32"""
     from fsnet_amd.configs import meta_arch_cfg
@@ -223,14 +197,8 @@ def test_evaluation_hook_end_to_end(dev, tree, tmp_path):
     from oracle import eval_oracle as EO
     raw, _, val, _ = tree
     h, w = 64, 64
-    aug = 'fsnet_amd.vision_base.data.augmentations.augmentations'
     ds = KITTI360FisheyeDataset(raw_path=raw, split_file=val, is_filter_static=False, use_right_image=False,
-                                augmentation=dict(name='fsnet_amd.vision_base.utils.builder.Sequential', cfg_list=[
-                                    dict(name=aug + '.ConvertToFloat'),
-                                    dict(name=aug + '.Resize', size=(h, w), preserve_aspect_ratio=False),
-                                    dict(name=aug + '.Normalize', mean=MEAN, stds=STD),
-                                    dict(name=aug + '.ConvertToTensor')],
-                                    image_keys=[('image', 0)], calib_keys=['P2']))
+                                augmentation=HK.val_augmentation(h, w))
     assert len(ds) == len(HK.EVAL_FRAMES)
     m = _fisheye_model(h, w, dev)
     hook = build(name="fsnet_amd.monodepth.pipeline_hooks.evaluation_hooks.base_evaluation_hooks.KittiEvaluationHook",
@@ -263,59 +231,22 @@ def test_training_step_from_the_dataset(dev, tree):
     host (numpy restatement of the resize and Normalize) and fed directly.  The two batches' images come from different
     code (kernel vs numpy) and agree to float32 rounding, so the losses are compared to 2e-5 relative, the bound of the
     fisheye training-step test against its oracle."""
-    from fsnet_amd.configs import training_cfg
-    from fsnet_amd.engine.runtime import RT
     from fsnet_amd.monodepth.data.datasets.fisheye_dataset import KITTI360FisheyeDataset
     from fsnet_amd.vision_base.data.augmentations.augmentations import DeviceAugment, PLAN
-    from fsnet_amd.vision_base.networks.optimizers.optimizers import build_optimizer
-    from fsnet_amd.vision_base.utils.builder import build
-    from oracle import augment_oracle as A
     raw, train, _, _ = tree
     h, w = 64, 64
-    fids = [0, -1, 1]
-    imgs, origs = [('image', i) for i in fids], [('original_image', i) for i in fids]
-    aug = 'fsnet_amd.vision_base.data.augmentations.augmentations'
     ds = KITTI360FisheyeDataset(raw_path=raw, split_file=train, use_right_image=True,
-                                augmentation=dict(name='fsnet_amd.vision_base.utils.builder.Sequential', cfg_list=[
-                                    dict(name=aug + '.ConvertToFloat'),
-                                    dict(name=aug + '.Resize', size=(h, w), preserve_aspect_ratio=False),
-                                    dict(name=aug + '.Normalize', mean=MEAN, stds=STD, image_keys=imgs),
-                                    dict(name=aug + '.Normalize', mean=np.zeros(3), stds=np.ones(3), image_keys=origs),
-                                    dict(name=aug + '.ConvertToTensor')],
-                                    image_keys=imgs, calib_keys=['P2'], gt_image_keys=['patched_mask']))
+                                augmentation=HK.train_augmentation(h, w, origs_in_image_keys=False))
     np.random.seed(1)
     samples = [ds[i] for i in range(4)]
     assert len({s["calib_meta"]["mirror_parameters"]["xi"] for s in samples}) == 2      # both cameras in the batch
-    # the same samples collated directly on the host
-    direct = {}
-    mean, std = MEAN.astype(np.float32), STD.astype(np.float32)
-    for f in fids:
-        res = [A.resize_linear(s[('image', f)].astype(np.float32), w, h) for s in samples]
-        direct[('image', f)] = torch.from_numpy(np.stack([((r / np.float32(255.0) - mean) / std).transpose(2, 0, 1)
-                                                          for r in res]).astype(np.float32))
-        direct[('original_image', f)] = torch.from_numpy(np.stack([(r / np.float32(255.0)).transpose(2, 0, 1)
-                                                                   for r in res]).astype(np.float32))
-    for f in fids[1:]:
-        direct[('relative_pose', f)] = torch.from_numpy(np.stack([s[('relative_pose', f)] for s in samples]))
-    direct['P2'] = torch.stack([s['P2'] for s in samples])
-    direct['calib_meta'] = [s['calib_meta'] for s in samples]
-    direct['patched_mask'] = torch.ones(len(samples), h, w, dtype=torch.float64)
-    direct = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in direct.items()}
-    batch = DeviceAugment(fids)([dict(s) for s in samples], dev)
+    direct = HK.direct_batch(samples, h, w, dev, fisheye=True)
+    batch = DeviceAugment([0, -1, 1])([dict(s) for s in samples], dev)
     assert PLAN not in batch and batch['patched_mask'].dtype == torch.float64 and batch['P2'].shape == (4, 3, 4)
     for k in list(direct):
         if isinstance(direct[k], torch.Tensor):
             print(k, float((batch[k].double() - direct[k].double()).abs().max()))
-    losses = []
-    for b in (batch, direct):
-        m = _fisheye_model(h, w, dev).train()
-        tc = training_cfg()
-        opt = build_optimizer(m, **tc.optimizer)
-        hook = build(use_graph=False, **tc.training_hook)
-        out = hook(dict(b), m, opt)
-        torch.cuda.synchronize()
-        losses.append(float(out["loss"].detach()))
-    RT.set_compute_dtype(torch.bfloat16)
+    losses = HK.step_losses((batch, direct), lambda: _fisheye_model(h, w, dev))
     print("losses", losses)
     assert np.isfinite(losses).all() and 0 < losses[0] < 10
     assert abs(losses[0] - losses[1]) <= 2e-5 * abs(losses[1])
