@@ -186,7 +186,7 @@ class FsMotionMaskArgs(C.Structure):
     ]
 
 
-ABI_VERSION = 15     # FS_ABI_VERSION of include/fsnet_hip.h (tests/test_abi.py holds the two together)
+ABI_VERSION = 15    # FS_ABI_VERSION of include/fsnet_hip.h (tests/test_abi.py holds the two together)
 _lib = None
 
 

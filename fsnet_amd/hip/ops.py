@@ -781,6 +781,48 @@ def depth_eval_masked(pred, gt, mask=None, lo=0.3, hi=60.0, crop=False):
     return out
 
 
+def _depth_operand(t, name):
+    """-> (contiguous tensor, is_u16).  float32, or 16-bit storage read as unsigned: torch.uint16, or torch.int16
+    holding the same bits (numpy `a.view(np.int16)` of a uint16 plane; torch builds without uint16 kernels can still
+    allocate, copy and slice int16)."""
+    assert t.is_cuda and t.dim() == 3, "%s: device tensor [N, H, W]" % name
+    if t.dtype == torch.float32:
+        return t.contiguous(), 0
+    if t.dtype in (torch.uint16, torch.int16):
+        return t.contiguous(), 1
+    raise TypeError("%s: float32, uint16 or int16 (read as uint16) expected, got %s" % (name, t.dtype))
+
+
+def depth_errors9(pred, gt, scale=256.0):
+    """The nine KITTI depth-benchmark metrics of N image pairs (fs_depth_errors9; kitti_supervised_eval.py:7-81).
+    pred, gt: device tensors [N, H, W] of equal shape, each float32 (metres) or uint16 (the raw PNG plane, value / scale
+    metres); int16 storage is accepted and read as uint16, bit for bit.  Returns f64 [N, 10] on the device: mae, rmse,
+    inverse mae, inverse rmse, log mae, log rmse, scale invariant log, abs relative, squared relative, n_valid."""
+    pred, pu = _depth_operand(pred, "pred")
+    gt, gu = _depth_operand(gt, "gt")
+    assert tuple(pred.shape) == tuple(gt.shape) and pred.device == gt.device
+    N, H, W = pred.shape
+    ws = int(lib.fs_depth_errors9_workspace_bytes(N, H, W))
+    if ws < 0:
+        raise ValueError("depth_errors9: bad shape N=%d H=%d W=%d" % (N, H, W))
+    workspace = torch.empty(ws // 8, dtype=torch.float64, device=pred.device)
+    out = torch.empty(N, 10, dtype=torch.float64, device=pred.device)
+    check(lib.fs_depth_errors9(pred.data_ptr(), gt.data_ptr(), pu, gu, float(scale), N, H, W, workspace.data_ptr(), ws,
+                               out.data_ptr(), stream_ptr()), "depth_errors9")
+    return out
+
+
+def depth_quantize_u16(depth, scale=256.0):
+    """depth: device fp32 [H, W] -> torch.uint16 [H, W] = trunc(depth * scale) saturated to [0, 65535], NaN -> 0
+    (fs_depth_quantize_u16: the KITTI devkit's uint16(depth * 256)).  `.cpu().numpy()` of the result is a uint16 array."""
+    assert depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 2
+    depth = depth.contiguous()
+    out = torch.empty(depth.shape, dtype=torch.int16, device=depth.device)
+    check(lib.fs_depth_quantize_u16(depth.data_ptr(), out.data_ptr(), float(scale), depth.shape[0], depth.shape[1],
+                                    stream_ptr()), "depth_quantize_u16")
+    return out.view(torch.uint16)
+
+
 class _LidarDepth:
     """What the LiDAR ground-truth ops share: the workspace, the scans of G frames as one `points` [N, 4] with
     `offsets` [G + 1] into it, and the `depth` maps.  Buffers are kept between calls of the same (G, H, W) so that a

@@ -85,15 +85,7 @@ class KittiDepthMonoDataset(torch.utils.data.Dataset):
         self.depth_path = getattr(data_cfg, 'depth_path', None)
         self.frame_idxs = data_cfg.frame_idxs
         self.imdb = read_split_file(data_cfg.split_file)
-        self.meta_dict = {}
-        for date_time in sorted(os.listdir(self.raw_path)):
-            folder_path = os.path.join(self.raw_path, date_time)
-            if not os.path.isdir(folder_path):
-                continue
-            P2, P3 = read_P23_from_sequence(os.path.join(folder_path, "calib_cam_to_cam.txt"))
-            self.meta_dict[date_time] = dict(
-                P2=P2, P3=P3, T_vel2cam=read_T_from_sequence(os.path.join(folder_path, "calib_velo_to_cam.txt")),
-                T_imu2vel=read_imu2velo(os.path.join(folder_path, "calib_imu_to_velo.txt")))
+        self.meta_dict = _read_meta(self.raw_path)
         self.pose_dict = {key: read_pose_mat(os.path.join(self.raw_path, key, 'oxts', 'pose.mat'))
                           for key in set(obj['folder'] for obj in self.imdb)}
         self.is_motion_mask = getattr(data_cfg, 'is_motion_mask', False)
@@ -160,3 +152,69 @@ class KittiDepthMonoDataset(torch.utils.data.Dataset):
 
     def get_flow(self, i):
         return read_flow_png(os.path.join(self.flow_path, f"{i:08d}.png"))
+
+
+def _read_meta(raw_path):
+    """per-date calibration of a KITTI raw tree, as KittiDepthMonoDataset reads it (entries that are not directories
+    are skipped)"""
+    meta = {}
+    for date_time in sorted(os.listdir(raw_path)):
+        folder_path = os.path.join(raw_path, date_time)
+        if not os.path.isdir(folder_path):
+            continue
+        P2, P3 = read_P23_from_sequence(os.path.join(folder_path, "calib_cam_to_cam.txt"))
+        meta[date_time] = dict(
+            P2=P2, P3=P3, T_vel2cam=read_T_from_sequence(os.path.join(folder_path, "calib_velo_to_cam.txt")),
+            T_imu2vel=read_imu2velo(os.path.join(folder_path, "calib_imu_to_velo.txt")))
+    return meta
+
+
+class KittiDepthMonoEigenTestDataset(torch.utils.data.Dataset):
+    """The Eigen test split as the reference's validation configs name it (mono_dataset.py:253-345; constructor keys
+    raw_path, split_file, augmentation and optionally depth_path).  No frame_idxs, static filter or patched_mask: a
+    sample is ('image', 0), ('image', -1) = the frame before (frame `index` itself again when index == 0),
+    ('original_image', 0), P2 / original_P2 by side, the float32 ('relative_pose', -1) and — only when `depth_path` is
+    among the config keys — ('sparse_depth', 0), which the reference reads from raw_path/<folder>/depth/%010d.png, not
+    from depth_path (:334-340); then the configured augmentation on a deep copy.  pose.mat is read per item (:342-345).
+
+    Quirk kept from the reference (:311): the poses are pose[[index, index - 1]], so at index == 0 the second one is
+    pose[-1], the drive's LAST pose, while the second frame is frame 0 again."""
+
+    def __init__(self, **data_cfg):
+        data_cfg = EasyDict(data_cfg)
+        super().__init__()
+        self.raw_path = data_cfg.raw_path
+        self.depth_path = data_cfg.depth_path if 'depth_path' in data_cfg else None
+        self.imdb = read_split_file(data_cfg.split_file)
+        self.meta_dict = _read_meta(self.raw_path)
+        self.transform = build(**data_cfg.augmentation)
+
+    def __getitem__(self, i):
+        obj = self.imdb[i]
+        folder, index, side, datetime = obj['folder'], obj['index'], obj['side'], obj['datetime']
+        data = dict()
+        data[("image", 0)] = self.get_color(folder, index, side)
+        data[("image", -1)] = self.get_color(folder, index - 1 if index > 0 else index, side)
+        data[('original_image', 0)] = data[('image', 0)].copy()
+        data['P2'] = self.meta_dict[datetime][{"l": "P2", "r": "P3"}[side]]
+        data['original_P2'] = data['P2'].copy()
+        imu2world = self.get_pose(folder, [index, index - 1])
+        meta = self.meta_dict[datetime]
+        data[('relative_pose', -1)] = cam_relative_pose(imu2world[0], imu2world[1], meta['T_imu2vel'],
+                                                        meta['T_vel2cam']).astype(np.float32)
+        if self.depth_path is not None:
+            data[('sparse_depth', 0)] = self.get_depth(folder, index, side)
+        return self.transform(deepcopy(data))
+
+    def __len__(self):
+        return len(self.imdb)
+
+    def get_color(self, folder, frame_index, side):
+        camera_folder = {"l": "image_02", "r": "image_03"}[side]
+        return read_image(os.path.join(self.raw_path, folder, camera_folder, 'data', '%010d.png' % frame_index))
+
+    def get_depth(self, folder, frame_index, side):
+        return read_depth(os.path.join(self.raw_path, folder, 'depth', '%010d.png' % frame_index))
+
+    def get_pose(self, folder, frame_indexes, *args, **kwargs):
+        return read_pose_mat(os.path.join(self.raw_path, folder, 'oxts', 'pose.mat'))[frame_indexes, :, :]

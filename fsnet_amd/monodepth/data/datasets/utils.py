@@ -54,9 +54,10 @@ def read_motion_mask(path):
 
 
 def read_png16(path):
-    """16-bit truecolour PNG (colour type 2, bit depth 16, not interlaced) -> uint16 [H, W, 3] in file channel order.
-    PIL opens such files as 8-bit RGB, so this decodes them with zlib: IHDR, the IDAT stream, filters 0-4.  Filters
-    None, Sub and Up are vectorised per row (a 375x1242 file in ~20 ms); Average and Paeth rows step one pixel at a
+    """16-bit truecolour PNG (colour type 2, bit depth 16, not interlaced) -> uint16 [H, W, 3] in file channel order;
+    16-bit greyscale (colour type 0: KITTI depth maps) -> uint16 [H, W].
+    PIL opens the truecolour files as 8-bit RGB, so this decodes them with zlib: IHDR, the IDAT stream, filters 0-4.
+    Filters None, Sub and Up are vectorised per row (a 375x1242 file in ~20 ms); Average and Paeth rows step one pixel at a
     time in numpy (seconds for a 375x1242 file made only of them).  write_png16 writes filter 0."""
     import struct
     import zlib
@@ -76,10 +77,11 @@ def read_png16(path):
             break
         pos += 12 + n
     W, H, depth, ctype, _, _, interlace = hdr
-    if depth != 16 or ctype != 2 or interlace != 0:
-        raise ValueError("%s: only 16-bit RGB non-interlaced PNGs are read here (bit depth %d, colour type %d)"
-                         % (path, depth, ctype))
-    bpp, stride = 6, W * 6
+    if depth != 16 or ctype not in (0, 2) or interlace != 0:
+        raise ValueError("%s: only 16-bit RGB or greyscale non-interlaced PNGs are read here (bit depth %d, colour "
+                         "type %d)" % (path, depth, ctype))
+    bpp = 6 if ctype == 2 else 2
+    stride = W * bpp
     raw = np.frombuffer(zlib.decompress(b''.join(idat)), np.uint8).reshape(H, stride + 1)
     out = np.zeros((H, stride), np.uint8)
     prev = np.zeros(stride, np.int64)
@@ -87,11 +89,11 @@ def read_png16(path):
         ft, line = raw[y, 0], raw[y, 1:].astype(np.int64)
         if ft == 0:
             cur = line
-        elif ft == 1:        # Sub: a running sum along each of the 6 byte lanes
+        elif ft == 1:        # Sub: a running sum along each of the bpp byte lanes
             cur = np.cumsum(line.reshape(W, bpp), axis=0).reshape(-1) & 255
         elif ft == 2:        # Up
             cur = (line + prev) & 255
-        elif ft in (3, 4):   # Average / Paeth: sequential along the row, one pixel (6 lanes) per step
+        elif ft in (3, 4):   # Average / Paeth: sequential along the row, one pixel (bpp lanes) per step
             cur = np.zeros(stride, np.int64)
             a = np.zeros(bpp, np.int64)
             c = np.zeros(bpp, np.int64)
@@ -109,21 +111,24 @@ def read_png16(path):
             raise ValueError("%s: PNG filter type %d" % (path, ft))
         out[y] = cur
         prev = cur
-    return out.reshape(H, W, 3, 2).astype(np.uint16) @ np.array([256, 1], np.uint16)
+    img = out.reshape(H, W, bpp // 2, 2).astype(np.uint16) @ np.array([256, 1], np.uint16)
+    return img if ctype == 2 else img[:, :, 0]
 
 
 def write_png16(path, img):
-    """uint16 [H, W, 3] -> 16-bit truecolour PNG (filter 0), the format read_png16 reads"""
+    """uint16 [H, W, 3] -> 16-bit truecolour PNG, uint16 [H, W] -> 16-bit greyscale PNG (filter 0): the formats
+    read_png16 reads"""
     import struct
     import zlib
     img = np.ascontiguousarray(np.asarray(img, '>u2'))
-    H, W, _ = img.shape
+    H, W = img.shape[:2]
+    ctype = 0 if img.ndim == 2 else 2
     raw = b''.join(b'\x00' + img[y].tobytes() for y in range(H))
 
     def chunk(kind, body):
         return struct.pack('>I', len(body)) + kind + body + struct.pack('>I', zlib.crc32(kind + body) & 0xffffffff)
     with open(path, 'wb') as f:
-        f.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', W, H, 16, 2, 0, 0, 0)) +
+        f.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', W, H, 16, ctype, 0, 0, 0)) +
                 chunk(b'IDAT', zlib.compress(raw)) + chunk(b'IEND', b''))
 
 

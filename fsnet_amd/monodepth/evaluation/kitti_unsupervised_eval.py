@@ -2,7 +2,8 @@
 kitti_unsupervised_eval.py:11-127).  `_single_loss` runs on the device: resize to the ground truth's size, valid mask
 + Garg crop, median scaling, clamp and the seven depth errors are one HIP launch per image (fs_depth_eval), so a
 validation pass does not copy depth maps to the host.  KittiEigenEvaluator exports its ground truth on the host
-(`_precompute`, :27-45, generate_depth_map); Kitti360Evaluator (:164-212) exports it on the device, with the loop
+(`_precompute`, :27-45, generate_depth_map) or, with export_on_device, through fs_lidar_pinhole_depth; called with a
+folder of saved predictions it scores those (:102-161).  Kitti360Evaluator (:164-212) exports it on the device, with the loop
 (Kitti360LidarExport) that Kitti360FisheyeEvaluator's export runs too."""
 import os
 
@@ -27,9 +28,14 @@ def stack_maps(maps):
 
 class KittiEigenEvaluator(object):
     def __init__(self, data_path=None, split_file=None, gt_saved_file=None, is_evaluate_absolute=False, gt_depths=None,
-                 device=None):
+                 device=None, export_on_device=False, group_size=8):
+        """export_on_device (an addition, default off): a missing ground-truth cache is exported by
+        fs_lidar_pinhole_depth, `group_size` scans per call (_precompute_on_device), instead of generate_depth_map
+        per scan on the host.  Same maps, same cache."""
         self.is_evaluate_absolute = is_evaluate_absolute
         self.device = device
+        self.export_on_device = bool(export_on_device)
+        self.group_size = int(group_size)
         if gt_depths is not None:
             self.gt_depths = gt_depths
         elif gt_saved_file is not None and os.path.isfile(gt_saved_file):
@@ -39,7 +45,10 @@ class KittiEigenEvaluator(object):
                 raise ValueError("KittiEigenEvaluator: no cached ground truth (gt_saved_file=%r) and no data_path / "
                                  "split_file to export it from" % (gt_saved_file,))
             print("Start exporting ground truth depths specified by %s to %s" % (split_file, gt_saved_file))
-            self._precompute(data_path, split_file, gt_saved_file)
+            if self.export_on_device:
+                self._precompute_on_device(data_path, split_file, gt_saved_file)
+            else:
+                self._precompute(data_path, split_file, gt_saved_file)
         self._gt_dev = {}
 
     def _precompute(self, data_path, split_file, gt_saved_file):
@@ -53,6 +62,42 @@ class KittiEigenEvaluator(object):
                 folder, frame_id, _ = line.split()
                 scan = os.path.join(data_path, folder, "velodyne_points/data", "{:010d}.bin".format(int(frame_id)))
                 gts.append(generate_depth_map(os.path.join(data_path, folder.split("/")[0]), scan, 2, True).astype(np.float32))
+        if gt_saved_file is not None:
+            np.savez_compressed(gt_saved_file, data=stack_maps(gts))
+        self.gt_depths = gts
+
+    def _precompute_on_device(self, data_path, split_file, gt_saved_file):
+        """_precompute with the projection on the device: per recording date P_velo2im and (H, W) as
+        generate_depth_map composes them (kitti_velo_to_image, f64 on the host); consecutive frames of one size, up to
+        `group_size`, are one fs_lidar_pinhole_depth call, each frame with its own matrix.  At most `group_size` scans
+        are held in host memory.  The maps equal generate_depth_map(..., 2, True).astype(float32) bit for bit."""
+        from fsnet_amd.monodepth.data.datasets.utils import read_pc_from_bin
+        from fsnet_amd.monodepth.networks.utils.monodepth_utils import kitti_velo_to_image
+        calib, frames = {}, []              # frames: (scan path, P [3, 4], h, w)
+        with open(split_file, "r") as f:
+            for line in f:
+                if not line.strip():
+                    continue
+                folder, frame_id, _ = line.split()
+                date = folder.split("/")[0]
+                if date not in calib:
+                    calib[date] = kitti_velo_to_image(os.path.join(data_path, date), 2)
+                P, (h, w) = calib[date]
+                frames.append((os.path.join(data_path, folder, "velodyne_points/data",
+                                            "{:010d}.bin".format(int(frame_id))), P, int(h), int(w)))
+        dev = self._device_for()
+        gts, op, start = [], None, 0
+        while start < len(frames):
+            h, w = frames[start][2:]
+            stop = start
+            while stop < len(frames) and stop - start < self.group_size and frames[stop][2:] == (h, w):
+                stop += 1
+            G = stop - start
+            if op is None or (op.G, op.H, op.W) != (G, h, w):
+                op = ops.LidarPinholeDepth(G, h, w, dev)
+            op.stage([read_pc_from_bin(fr[0]) for fr in frames[start:stop]], np.stack([fr[1] for fr in frames[start:stop]]))
+            gts.extend(op.run().cpu().numpy())
+            start = stop
         if gt_saved_file is not None:
             np.savez_compressed(gt_saved_file, data=stack_maps(gts))
         self.gt_depths = gts
@@ -101,6 +146,37 @@ class KittiEigenEvaluator(object):
         if is_print:
             print(log_str)
         return log_str
+
+
+    def __call__(self, result_path, writer=None, global_step=0, epoch_num=0):
+        """The Eigen metric over a folder of saved predictions, 16-bit PNGs of depth * 256 in the order of the ground
+        truth (reference :102-161; KittiEvaluationHook(save_depth_dir=...) writes such a folder).  Per file: read_depth,
+        then fs_depth_eval against the cached ground truth, as for a live prediction.  Prints the reference's log with
+        the mean and standard deviation of the median ratios; returns what the hooks return (the reference returns
+        None), or None when the file count differs from the ground truth's."""
+        from fsnet_amd.monodepth.data.datasets.utils import read_depth
+        filelist = sorted(os.listdir(result_path))
+        if len(filelist) != len(self.gt_depths):
+            print(f"The length of pred_depths is {len(filelist)} while the length of gt_depths is {len(self.gt_depths)}")
+            print("Drop evaluation")
+            return None
+        dev = self._device_for()
+        rows = [self.device_errors(torch.from_numpy(read_depth(os.path.join(result_path, name))).to(dev), i)
+                for i, name in enumerate(filelist)]
+        res = torch.stack(rows).cpu().numpy()
+        if (res[:, 15] == 0).any():
+            raise ValueError
+        mean_errors, mean_abs_errors, scales = res[:, 1:8].mean(0), res[:, 8:15].mean(0), res[:, 0]
+        log_str = f"Epoch {epoch_num} | Scaled Error | {scales.mean()}, {scales.std()}"
+        log_str += "\n  " + ("{:>8} | " * 7).format("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
+        log_str += "\n" + ("&{: 8.3f}  " * 7).format(*mean_errors.tolist()) + "\\\\"
+        log_str += f"\nEpoch {epoch_num} | Abs Error without Scaled"
+        log_str += "\n  " + ("{:>8} | " * 7).format("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
+        log_str += "\n" + ("&{: 8.3f}  " * 7).format(*mean_abs_errors.tolist()) + "\\\\"
+        if writer is not None:
+            writer.add_text("evaluation logs", log_str.replace(' ', '&nbsp;').replace('\n', '  \n'), global_step=epoch_num)
+        print(log_str)
+        return dict(mean_errors=mean_errors, mean_abs_errors=mean_abs_errors, ratios=scales)
 
 
 class Kitti360LidarExport(object):
@@ -154,8 +230,8 @@ class Kitti360Evaluator(Kitti360LidarExport, KittiEigenEvaluator):
 
     def __init__(self, data_path=None, split_file=None, gt_saved_file=None, is_evaluate_absolute=False, gt_depths=None,
                  device=None, group_size=8):
-        self.group_size = int(group_size)
-        super().__init__(data_path, split_file, gt_saved_file, is_evaluate_absolute, gt_depths, device)
+        super().__init__(data_path, split_file, gt_saved_file, is_evaluate_absolute, gt_depths, device,
+                         group_size=group_size)
 
     def _load_calib(self, calib_dir):
         from fsnet_amd.monodepth.data.datasets.kitti360_dataset import read_P01_from_sequence, read_T_from_sequence

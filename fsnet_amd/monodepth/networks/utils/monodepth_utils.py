@@ -83,8 +83,9 @@ def sub2ind(matrix_size, row, col):
     return row * (n - 1) + col - 1
 
 
-def generate_depth_map(calib_dir, velo_filename, cam=2, vel_depth=False):
-    """velodyne scan -> sparse depth image of camera `cam` ([H, W] float64, 0 = no return)"""
+def kitti_velo_to_image(calib_dir, cam=2):
+    """(P_velo2im [3, 4] f64 = P_rect_0<cam> . R_rect_00 . velo2cam, im_shape int32 [H, W] from S_rect_02) of one
+    recording date, composed as generate_depth_map composes them"""
     import os
     import numpy as np
     cam2cam = read_calib_file(os.path.join(calib_dir, "calib_cam_to_cam.txt"))
@@ -94,7 +95,12 @@ def generate_depth_map(calib_dir, velo_filename, cam=2, vel_depth=False):
     R_cam2rect = np.eye(4)
     R_cam2rect[:3, :3] = cam2cam["R_rect_00"].reshape(3, 3)
     P_velo2im = np.dot(np.dot(cam2cam["P_rect_0" + str(cam)].reshape(3, 4), R_cam2rect), velo2cam)
+    return P_velo2im, im_shape
 
+
+def generate_depth_map(calib_dir, velo_filename, cam=2, vel_depth=False):
+    """velodyne scan -> sparse depth image of camera `cam` ([H, W] float64, 0 = no return)"""
+    P_velo2im, im_shape = kitti_velo_to_image(calib_dir, cam)
     velo = load_velodyne_points(velo_filename)
     velo = velo[velo[:, 0] >= 0, :]                       # in front of the sensor (approximation of "in front of the camera")
     return _export_depth(velo, P_velo2im, im_shape, vel_depth)

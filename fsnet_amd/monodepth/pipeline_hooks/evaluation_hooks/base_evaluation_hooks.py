@@ -5,12 +5,16 @@ Everything between the network output and the 15 numbers per image stays on the 
 invert, then the evaluator's device_errors: fs_depth_eval for KITTI, fs_depth_eval_masked for the KITTI-360 fisheye
 evaluator); only those numbers are copied back.  Samples of the mirrored augmentation classes (raw frames plus a
 device plan, e.g. KITTI360FisheyeDataset with its validation Resize) are collated and resized by DeviceAugment.  KittiEvaluationHook_postopt (:69-127) refines the
-prediction with sparse visual-odometry depth first (ops.post_optimize, one call per batch on the device)."""
+prediction with sparse visual-odometry depth first (ops.post_optimize, one call per batch on the device).  Both hooks
+take an optional `save_depth_dir` and then also write every frame's prediction as a 16-bit PNG (_save_depth)."""
+import os
+
 import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
 from fsnet_amd.hip import ops
+from fsnet_amd.monodepth.data.datasets.utils import write_png16
 from fsnet_amd.monodepth.networks.utils import postopt_utils as PU
 from fsnet_amd.vision_base.data.augmentations.augmentations import PLAN, DeviceAugment
 from fsnet_amd.vision_base.data.datasets.dataset_utils import collate_fn
@@ -45,11 +49,22 @@ def _original_hw(batched_data, i):
 
 
 class KittiEvaluationHook(object):
-    def __init__(self, test_run_hook_cfg, dataset_eval_cfg=None, **kwargs):
+    def __init__(self, test_run_hook_cfg, dataset_eval_cfg=None, save_depth_dir=None, **kwargs):
         self.test_hook = build(**test_run_hook_cfg)
         self.dataset_eval_func = None if dataset_eval_cfg is None else build(**dataset_eval_cfg)
+        self.save_depth_dir = save_depth_dir
         for key in kwargs:
             setattr(self, key, kwargs[key])
+
+    def _save_depth(self, depth_0, frame_index):
+        """with save_depth_dir (an addition; None = nothing is written): the full-resolution prediction as
+        <save_depth_dir>/<frame_index:010d>.png, uint16(depth * 256) — what KittiEigenEvaluator.__call__ and
+        kitti_supervised_eval read.  Quantised on the device (fs_depth_quantize_u16), copied back as two bytes per pixel."""
+        if self.save_depth_dir is None:
+            return
+        os.makedirs(self.save_depth_dir, exist_ok=True)
+        write_png16(os.path.join(self.save_depth_dir, "%010d.png" % frame_index),
+                    ops.depth_quantize_u16(depth_0).cpu().numpy())
 
     @torch.no_grad()
     def __call__(self, meta_arch, dataset_val, writer=None, global_step=0, epoch_num=0):
@@ -70,6 +85,7 @@ class KittiEvaluationHook(object):
                 h, w = _original_hw(batched_data, i)
                 depth_0 = ops.resize_linear(depth, h, w, invert=True)          # 1 / cv2.resize(1 / depth, (w, h))
                 rows.append(self.dataset_eval_func.device_errors(depth_0, frame_index))
+                self._save_depth(depth_0, frame_index)
                 frame_index += 1
         res = torch.stack(rows).cpu().numpy()
         if (res[:, 15] == 0).any():
@@ -158,6 +174,7 @@ class KittiEvaluationHook_postopt(KittiEvaluationHook):
                 h, w = _original_hw(batched_data, i)
                 depth_0 = ops.resize_linear(crops[i], h, w, invert=True)          # 1 / cv2.resize(1 / depth, (w, h))
                 rows.append(self.dataset_eval_func.device_errors(depth_0, frame_index))
+                self._save_depth(depth_0, frame_index)
                 frame_index += 1
         res = torch.stack(rows).cpu().numpy()
         if (res[:, 15] == 0).any():

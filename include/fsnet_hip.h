@@ -32,7 +32,8 @@ extern "C" {
 #define FS_STAT_SLOTS 8
 
 /* library/ABI version and the ISA the kernels were compiled for ("gfx950").  FS_ABI_VERSION changes whenever an
- * argument struct or a signature below does; a host binding refuses a library that reports another number. */
+ * argument struct or a signature below does (added entry points leave it: no earlier caller is affected); a host binding
+ * refuses a library that reports another number. */
 #define FS_ABI_VERSION 15
 int fs_abi_version(void);
 const char* fs_target_arch(void);
@@ -380,6 +381,24 @@ int64_t fs_lidar_mei_depth_workspace_bytes(int G, int H, int W);
 int fs_lidar_pinhole_depth(const float* points, const int64_t* offsets, int64_t n_points, const double* P, int G, int H,
                            int W, float* depth, void* workspace, int64_t workspace_bytes, void* stream);
 int64_t fs_lidar_pinhole_depth_workspace_bytes(int G, int H, int W);
+
+/* Supervised KITTI depth-benchmark metrics (added under ABI 15, which no existing signature leaves): compute_errors of monodepth/evaluation/kitti_supervised_eval.py:7-81
+ * for N image pairs [N][H][W] in one call, with the `cv2.imread(path, -1) / scale` of :102 and :138-139 folded in.
+ * pred / gt: device uint16 (x_is_u16 != 0; the value is (double)v / scale) or float32 (widened to f64; scale unused), each
+ * aligned to its element size only.  Per image, over the pixels with gt > 0.01, in f64 and the reference's operation
+ * order, no clamp and no resize: out[n] = { mae, rmse, inverse mae, inverse rmse, log mae, log rmse, scale invariant log,
+ * abs relative, squared relative, n_valid }; n_valid == 0 leaves zeros (the reference divides by zero).  workspace: at
+ * least fs_depth_errors9_workspace_bytes(N, H, W) bytes, 8-byte aligned (the blocks' partial sums; -1: N, H or W < 1,
+ * N > 65535, H*W >= 2^31).  FS_EINVAL also for scale <= 0.  No host sync: capturable.  No floating-point atomics, and the
+ * pixels are divided among lanes by their index inside the image: the same bits for any run, any position of an image in
+ * its batch and any grouping of images into calls. */
+int fs_depth_errors9(const void* pred, const void* gt, int pred_is_u16, int gt_is_u16, double scale, int N, int H, int W,
+                     void* workspace, int64_t workspace_bytes, double* out, void* stream);
+int64_t fs_depth_errors9_workspace_bytes(int N, int H, int W);
+/* fs_depth_quantize_u16 (added under ABI 15): the KITTI devkit's `uint16(depth * 256)` for saved predictions (what read_depth,
+ * monodepth/data/datasets/utils.py:32-40, and kitti_supervised_eval.py:102 read back), made total: out[H][W] uint16 =
+ * trunc(depth * scale) in float32, saturated to [0, 65535], NaN -> 0.  FS_EINVAL for H, W < 1 or scale <= 0. */
+int fs_depth_quantize_u16(const float* depth, void* out, float scale, int H, int W, void* stream);
 
 /* Sparse-VO depth post-optimisation (postopt_utils.py:8-11, 94-226; KittiEvaluationHook_postopt,
  * base_evaluation_hooks.py:69-127), B images in one fixed launch sequence (capturable: no host sync, the launch count

@@ -682,6 +682,49 @@ def gen_kitti_dataset():
     np.savez_compressed(os.path.join(GOLD, "kitti_dataset.npz"), **out)
 
 
+def gen_kitti_eigen_test_dataset():
+    """the REAL KittiDepthMonoEigenTestDataset (mono_dataset.py:253-345) over the seeded tree of
+    tests/helpers_kitti_eigen.py, once with depth_path among the config keys and once without"""
+    import tempfile
+    from tests import helpers_kitti_eigen as HE
+    from monodepth.data.datasets.mono_dataset import KittiDepthMonoEigenTestDataset
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        raw, split = HE.make_eigen_tree(d)
+        for with_depth, tag in ((True, "d"), (False, "n")):
+            ds = KittiDepthMonoEigenTestDataset(**HE.eigen_cfg(raw, split, prefix='', with_depth=with_depth))
+            out["n"] = len(ds)
+            out["index"] = np.array([[o["index"], 0 if o["side"] == "l" else 1] for o in ds.imdb])
+            for i in range(len(ds)):
+                smp = ds[i]
+                out["%s%d_keys" % (tag, i)] = np.array(sorted(repr(k) for k in smp))
+                if with_depth:
+                    out["d%d_sparse_depth" % i] = np.asarray(smp[("sparse_depth", 0)])
+                    continue
+                out["s%d_image_0" % i], out["s%d_image_m" % i] = npy(smp[("image", 0)]), npy(smp[("image", -1)])
+                out["s%d_orig_0" % i] = npy(smp[("original_image", 0)])
+                out["s%d_pose_m" % i] = np.asarray(smp[("relative_pose", -1)])
+                out["s%d_P2" % i], out["s%d_original_P2" % i] = np.asarray(smp["P2"]), np.asarray(smp["original_P2"])
+    print("kitti eigen test dataset: %d samples, (index, side) %s" % (out["n"], out["index"].tolist()))
+    np.savez_compressed(os.path.join(GOLD, "kitti_eigen_test_dataset.npz"), **out)
+
+
+def gen_supervised_eval():
+    """the REAL compute_errors (kitti_supervised_eval.py:7-81; numba's jit is the identity shim, so the double loop runs
+    as plain Python) on the seeded uint16 pairs of tests/helpers_supervised_eval.py, divided by 256 as evaluate_depth
+    divides what cv2.imread returns"""
+    from tests import helpers_supervised_eval as HS
+    from monodepth.evaluation.kitti_supervised_eval import compute_errors
+    out = {}
+    for k, (H, W) in enumerate(HS.GOLDEN_SHAPES):
+        gt, pred = HS.u16_pair(H, W, seed=100 + k)
+        out["gt_%dx%d" % (H, W)], out["pred_%dx%d" % (H, W)] = gt, pred
+        out["errors_%dx%d" % (H, W)] = np.asarray(compute_errors(gt / 256.0, pred / 256.0), np.float64)
+        print("supervised eval %dx%d: %d valid, errors %s" % (H, W, int((gt / 256.0 > 0.01).sum()),
+                                                               np.array2string(out["errors_%dx%d" % (H, W)], precision=4)))
+    np.savez_compressed(os.path.join(GOLD, "supervised_eval.npz"), **out)
+
+
 def gen_kitti360_fisheye():
     """the REAL KITTI360FisheyeDataset (fisheye_dataset.py:107-262) and Kitti360FisheyeEvaluator
     (kitti360_fisheye_eval.py:15-145) over the seeded fake KITTI-360 tree of tests/helpers_kitti360.py: filtered index
@@ -1320,6 +1363,12 @@ if __name__ == "__main__":
     if "--only-kitti" in sys.argv:
         gen_kitti_dataset()
         sys.exit(0)
+    if "--only-kitti-eigen" in sys.argv:
+        gen_kitti_eigen_test_dataset()
+        sys.exit(0)
+    if "--only-supervised-eval" in sys.argv:
+        gen_supervised_eval()
+        sys.exit(0)
     if "--only-r50fx" in sys.argv:
         gen_model_r50fx()
         sys.exit(0)
@@ -1333,6 +1382,8 @@ if __name__ == "__main__":
     gen_fisheye()
     gen_model_r50fx()
     gen_kitti_dataset()
+    gen_kitti_eigen_test_dataset()
+    gen_supervised_eval()
     gen_kitti360_fisheye()
     gen_kitti360_persp()
     gen_loss_options()

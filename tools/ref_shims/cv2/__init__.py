@@ -81,7 +81,8 @@ def imread(path, flags=1):
     assert flags == IMREAD_UNCHANGED
     with open(path, "rb") as f:
         head = f.read(26)
-    if head[24] == 16:                                     # 16-bit: cv2 returns BGR
+    if head[24] == 16:                                     # 16-bit: cv2 returns BGR, or [H, W] for greyscale
         from fsnet_amd.monodepth.data.datasets.utils import read_png16
-        return read_png16(path)[:, :, ::-1].copy()
+        img = read_png16(path)
+        return img[:, :, ::-1].copy() if img.ndim == 3 else img
     return np.array(Image.open(path))
