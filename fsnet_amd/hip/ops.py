@@ -835,8 +835,11 @@ class _LidarDepth:
             raise ValueError("%s: bad shape G=%d H=%d W=%d" % (name, G, H, W))
         self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
         self.offsets = torch.zeros(G + 1, dtype=torch.int64, device=self.device)
-        self.depth = torch.empty(G, H, W, dtype=torch.float32, device=self.device)
+        self.depth = self._alloc_depth()
         self.points = torch.empty(0, 4, dtype=torch.float32, device=self.device)
+
+    def _alloc_depth(self):
+        return torch.empty(self.G, self.H, self.W, dtype=torch.float32, device=self.device)
 
     def _stage_scans(self, scans):
         """scans: G float32 [Ni, 4] arrays / tensors"""
@@ -915,6 +918,43 @@ def lidar_pinhole_depth(scans, P, H, W, device):
     """one call: G = len(scans) frames -> depth fp32 [G, H, W] on `device`"""
     op = LidarPinholeDepth(len(scans), H, W, device)
     op.stage(scans, P)
+    return op.run()
+
+
+class LidarNuscDepth(_LidarDepth):
+    """The nuScenes ground-truth export, G samples x C cameras per call (fs_lidar_nusc_depth_u16;
+    nuscenes_unsupervised_eval.py:85-126 and the uint16 cast of :198).  `depth` is the PNG plane: torch.uint16
+    [G, C, H, W] (int16 storage holding the same bits)."""
+
+    def __init__(self, G, C, H, W, device):
+        self.C = int(C)
+        super().__init__("lidar_nusc_depth", lambda g, h, w: lib.fs_lidar_nusc_depth_workspace_bytes(g, self.C, h, w),
+                         G, H, W, device)
+        self.M = torch.zeros(G, self.C, 12, dtype=torch.float64, device=self.device)
+
+    def _alloc_depth(self):
+        return torch.empty(self.G, self.C, self.H, self.W, dtype=torch.int16, device=self.device)
+
+    def stage(self, scans, M):
+        """scans: G float32 [Ni, 4] arrays / tensors (ego-frame x, y, z, one unused lane); M: f64 [G, C, 3, 4], rows
+        0..2 of homo_intrinsics @ inv(extrinsics)"""
+        self._stage_scans(scans)
+        self._stage_f64(self.M, M)
+
+    def run(self):
+        check(lib.fs_lidar_nusc_depth_u16(self._points_ptr(), self.offsets.data_ptr(), int(self.points.shape[0]),
+                                          self.M.data_ptr(), self.G, self.C, self.H, self.W, self.depth.data_ptr(),
+                                          self.workspace.data_ptr(), self.workspace.numel(), stream_ptr()),
+              "lidar_nusc_depth_u16")
+        return self.depth.view(torch.uint16)
+
+
+def lidar_nusc_depth_u16(scans, M, H, W, device):
+    """one call: G = len(scans) samples, C = M.shape[1] cameras -> torch.uint16 [G, C, H, W] on `device`"""
+    import numpy as np
+    M = np.asarray(M, dtype=np.float64)
+    op = LidarNuscDepth(len(scans), M.shape[1], H, W, device)
+    op.stage(scans, M)
     return op.run()
 
 

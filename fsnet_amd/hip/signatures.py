@@ -48,6 +48,9 @@ SIGNATURES = {
     # ABI 15: project_depth_map / generate_depth_map(vel_depth=True) (monodepth_utils.py:368-458)
     "fs_lidar_pinhole_depth": (C.c_int, [P, P, L, P, I, I, I, P, P, L, P]),
     "fs_lidar_pinhole_depth_workspace_bytes": (C.c_int64, [I, I, I]),
+    # added under ABI 15: generate_depth_map + the uint16 cast of nuscenes_unsupervised_eval.py:85-126, :198
+    "fs_lidar_nusc_depth_u16": (C.c_int, [P, P, L, P, I, I, I, I, P, P, L, P]),
+    "fs_lidar_nusc_depth_workspace_bytes": (C.c_int64, [I, I, I, I]),
     # added under ABI 15: compute_errors of kitti_supervised_eval.py:7-81 and the depth writer that feeds it
     "fs_depth_errors9": (C.c_int, [P, P, I, I, D, I, I, I, P, L, P, P]),
     "fs_depth_errors9_workspace_bytes": (C.c_int64, [I, I, I]),

@@ -38,6 +38,15 @@ def cam_relative_pose(T_imu2world_0, T_imu2world_1, T_imu2vel, T_vel2cam):
         @ np.linalg.inv(T_vel2cam)
 
 
+def get_transformation_matrix(translation, rotation):
+    """T [4, 4] from a translation [x, y, z] and a quaternion [w, x, y, z] (reference :59-67)"""
+    from scipy.spatial.transform import Rotation
+    T = np.eye(4)
+    T[0:3, 0:3] = Rotation.from_quat([rotation[1], rotation[2], rotation[3], rotation[0]]).as_matrix()
+    T[0:3, 3] = translation
+    return T
+
+
 def read_vo_depth(path):
     """sparse visual-odometry depth, 16-bit PNG -> float64 metres: / 65535 * 120, values < 3 or > 80 set to 120 (the
     reference's marker for "no point"; postopt_utils.py:50-53 reads it with cv2.imread(path, -1))"""

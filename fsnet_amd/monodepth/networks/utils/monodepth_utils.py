@@ -124,6 +124,14 @@ def _export_depth(velo, P_velo2im, im_shape, vel_depth):
         pts[:, 2] = velo[:, 0]
     pts[:, 0] = np.round(pts[:, 0]) - 1                   # (- 1: the KITTI matlab convention)
     pts[:, 1] = np.round(pts[:, 1]) - 1
+    return scatter_depth(pts, im_shape)
+
+
+def scatter_depth(pts, im_shape):
+    """pts [N, 3] f64 = (col, row, value) with col / row already rounded, in scan order -> [H, W] f64: the range test,
+    the last-writer scatter and the duplicate pass of the KITTI export, which the nuScenes export
+    (nuscenes_unsupervised_eval.generate_depth_map) runs too"""
+    import numpy as np
     ok = (pts[:, 0] >= 0) & (pts[:, 1] >= 0) & (pts[:, 0] < im_shape[1]) & (pts[:, 1] < im_shape[0])
     pts = pts[ok, :]
     rows, cols = pts[:, 1].astype(int), pts[:, 0].astype(int)

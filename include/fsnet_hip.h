@@ -382,6 +382,24 @@ int fs_lidar_pinhole_depth(const float* points, const int64_t* offsets, int64_t 
                            int W, float* depth, void* workspace, int64_t workspace_bytes, void* stream);
 int64_t fs_lidar_pinhole_depth_workspace_bytes(int G, int H, int W);
 
+/* LiDAR ground truth of the nuScenes evaluation (added under ABI 15): generate_depth_map followed by
+ * (depth * 256).astype(np.uint16) (nuscenes_unsupervised_eval.py:85-126, :198), G samples x C cameras per call.
+ * points / offsets as in fs_lidar_pinhole_depth: float32 [n_points][4] = ego-frame x, y, z and one unused lane, 16-byte
+ * aligned; the points of sample g are shared by its C cameras.  M: device f64 [G][C][12], rows 0..2 of
+ * homo_intrinsics @ inv(extrinsics).  Per point and camera, in f64 and this order (no FMA):
+ * p_k = m_k0 x + m_k1 y + m_k2 z + m_k3; kept iff p2 > 0 (a NaN fails); col = rint(p0 / p2) - 1, row = rint(p1 / p2) - 1
+ * (half to even); kept iff 0 <= col < W, 0 <= row < H; its value is q = min(trunc(p2 * 256.0), 65535).
+ * depth_u16 [G][C][H][W] uint16: a pixel takes the q of its last kept point in scan order; then, for every group of more
+ * than one point sharing the export index row * (W - 1) + col - 1 (one pixel, or the pair (r, W-1) / (r+1, 0)), the
+ * pixel of the group's first point takes the group's minimum q; 0 where no point lands.
+ * Deviation: for p2 >= 256 m the reference's uint16 cast wraps; this saturates at 65535 (beyond the sensor's range).
+ * workspace: at least fs_lidar_nusc_depth_workspace_bytes(G, C, H, W) bytes, 16-byte aligned (-1: G, C, H < 1, W < 2,
+ * G*C > 65535 or G*C*H*W >= 2^31; the main call returns FS_EINVAL for those).  No host sync: capturable.  Integer
+ * atomics only: the same bits for any run, any grouping of samples into calls and under graph replay. */
+int fs_lidar_nusc_depth_u16(const float* points, const int64_t* offsets, int64_t n_points, const double* M, int G, int C,
+                            int H, int W, void* depth_u16, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t fs_lidar_nusc_depth_workspace_bytes(int G, int C, int H, int W);
+
 /* Supervised KITTI depth-benchmark metrics (added under ABI 15, which no existing signature leaves): compute_errors of monodepth/evaluation/kitti_supervised_eval.py:7-81
  * for N image pairs [N][H][W] in one call, with the `cv2.imread(path, -1) / scale` of :102 and :138-139 folded in.
  * pred / gt: device uint16 (x_is_u16 != 0; the value is (double)v / scale) or float32 (widened to f64; scale unused), each

@@ -900,6 +900,154 @@ def gen_kitti360_persp():
     np.savez_compressed(os.path.join(GOLD, "kitti360_persp.npz"), **out)
 
 
+def gen_nusc():
+    """the REAL NusceneJsonDataset / NusceneDepthMonoDataset / NusceneSweepDepthMonoDataset (nuscene_dataset.py:14-238),
+    NuscenesEvaluator._precompute and _single_loss (nuscenes_unsupervised_eval.py:17-255) and FastNuscEvaluationHook
+    (base_evaluation_hooks.py:141-202) over the seeded tree of tests/helpers_nusc.py, with the devkit and pyquaternion
+    stand-ins of tools/ref_shims (this project's reading of the two packages, not pinned against the real ones).
+    The reference's generate_depth_map uses np.int, which NumPy 2 removed: set for this run.  Fixture conditions,
+    asserted: per sample at least one exact .5 tie, one merged edge pair and 100 pixels hit twice or more in
+    CAM_FRONT, and this package's explicit-order mirror equal to the reference's PNGs with zero differing pixels."""
+    import tempfile
+    import warnings
+    import cv2
+    from tests import helpers_nusc as HN
+    from oracle import eval_oracle as EO
+    np.int = int
+    import monodepth.evaluation.nuscenes_unsupervised_eval as RE
+    from monodepth.data.datasets.nuscene_dataset import (NusceneDepthMonoDataset, NusceneJsonDataset,
+                                                         NusceneSweepDepthMonoDataset)
+    from monodepth.pipeline_hooks.evaluation_hooks.base_evaluation_hooks import FastNuscEvaluationHook
+    from vision_base.data.datasets.nuscenes_utils import NuScenes
+    from fsnet_amd.monodepth.data.datasets.utils import read_png16
+    from fsnet_amd.monodepth.evaluation import nuscenes_unsupervised_eval as ME
+    out = {}
+    resize = cv2.resize
+    cv2.resize = lambda src, dsize, interpolation=cv2.INTER_LINEAR: (
+        EO.cv2_resize_linear(src, dsize[0], dsize[1]) if np.ndim(src) == 2 and interpolation == cv2.INTER_LINEAR
+        else resize(src, dsize, interpolation))
+    with tempfile.TemporaryDirectory() as d:
+        tree = HN.make_tree(d)
+        nusc = NuScenes(version=HN.VERSION, dataroot=tree["dataroot"], verbose=False)
+        resolved = []
+        get = nusc.get
+        nusc.get = lambda table, token: (resolved.append((table, token)), get(table, token))[1]
+        # ---- datasets ------------------------------------------------------------------------------------------
+        ds = NusceneJsonDataset(json_path=tree["json_train"], augmentation=HN.raw_augmentation(''))
+        out["json_n"] = np.array(len(ds))
+        for i in range(len(ds)):
+            out["json_keys"] = np.array(HN.flatten_sample(ds[i], "json%d_" % i, out))
+        val = NusceneJsonDataset(json_path=tree["json_val"], image_keys=['frame0'], frame_ids=[0],
+                                 augmentation=HN.raw_augmentation(''))
+        out["jsonval_keys"] = np.array(HN.flatten_sample(val[3], "jsonval3_", out))
+        tall = NusceneJsonDataset(json_path=tree["json_tall"], image_keys=['frame0'], frame_ids=[0],
+                                  augmentation=HN.raw_augmentation(''))
+        for i in range(2):
+            pm = tall[i]["patched_mask"]
+            assert pm.dtype == np.float64 and pm.shape == (HN.TALL_H, HN.TALL_W)
+            out["tall%d_mask_rows" % i] = pm.min(1)
+        assert out["tall0_mask_rows"][700:].max() == 0 and out["tall0_mask_rows"][:700].min() == 1
+        assert out["tall1_mask_rows"].min() == 1
+        for tag, cls in (("mono", NusceneDepthMonoDataset), ("sweep", NusceneSweepDepthMonoDataset)):
+            for filt in (False, True):
+                t = NusceneDepthMonoDataset.__init__
+                dsm = cls(split_file=tree["split"], nuscenes_version=HN.VERSION, nuscenes_dir=tree["dataroot"],
+                          is_filter_static=filt, filter_threshold=1.1005 if filt else 0.03,
+                          augmentation=HN.raw_augmentation(''))
+                assert dsm.nusc is nusc and t is NusceneDepthMonoDataset.__init__
+                np.random.seed(5)
+                k = "%s%d" % (tag, int(filt))
+                out[k + "_n"] = np.array(len(dsm))
+                for i in range(len(dsm)):
+                    out[k + "_keys"] = np.array(HN.flatten_sample(dsm[i], "%s_%d_" % (k, i), out, digest_frames=True))
+        # ---- ground-truth export ---------------------------------------------------------------------------------
+        f64_maps = []
+        ref_gdm = RE.generate_depth_map
+        RE.generate_depth_map = lambda *a, **k: (f64_maps.append(ref_gdm(*a, **k)), f64_maps[-1])[1]
+        gt_dir = os.path.join(d, "samples_depth_gt")
+        ev = RE.NuscenesEvaluator(tree["dataroot"], tree["split"], gt_dir, nuscenes_version=HN.VERSION)
+        RE.generate_depth_map = ref_gdm
+        out["gt_f64"] = np.array(f64_maps).reshape(len(HN.EVAL), len(HN.CAMS), HN.H, HN.W)
+        pngs, stats = [], []
+        for j, i in enumerate(HN.EVAL):
+            rec = get('sample', 'sample_%d' % i)
+            lidar_data, lidar_mask = ME.get_lidar(nusc, rec)
+            ref_data, ref_mask = RE.get_lidar(nusc, rec)
+            assert np.array_equal(lidar_data, ref_data) and np.array_equal(lidar_mask, ref_mask)
+            lidar = lidar_data[lidar_mask == 1, :]
+            planes = []
+            for c, cam in enumerate(HN.CAMS):
+                samp = get('sample_data', rec['data'][cam])
+                png = read_png16(samp['filename'].replace('samples', gt_dir).replace('.jpg', '.png'))
+                sens = get('calibrated_sensor', samp['calibrated_sensor_token'])
+                T = ME.camera_extrinsics(sens)
+                M = ME.projection_matrix(T, np.array(sens['camera_intrinsic']))[:3]
+                mine = ME.nusc_depth_u16(lidar, M, [HN.H, HN.W])
+                bad = int((mine != png).sum())
+                bad64 = int((ME.generate_depth_map(lidar, T, np.array(sens['camera_intrinsic']),
+                                                   im_shape=[HN.H, HN.W]) != out["gt_f64"][j, c]).sum())
+                assert png.dtype == np.uint16 and bad == 0 and bad64 == 0, (i, cam, bad, bad64)
+                planes.append(png)
+                if cam == 'CAM_FRONT':
+                    x, y, z = (lidar[:, k].astype(np.float64) for k in range(3))
+                    p = [M[k, 0] * x + M[k, 1] * y + M[k, 2] * z + M[k, 3] for k in range(3)]
+                    keep = p[2] > 0
+                    u, v = p[0][keep] / p[2][keep], p[1][keep] / p[2][keep]
+                    col, row = np.rint(u) - 1, np.rint(v) - 1
+                    ok = (col >= 0) & (row >= 0) & (col < HN.W) & (row < HN.H)
+                    hits = np.bincount((row[ok] * HN.W + col[ok]).astype(np.int64), minlength=HN.H * HN.W).reshape(HN.H, HN.W)
+                    ties = int((((u[ok] % 1) == 0.5) | ((v[ok] % 1) == 0.5)).sum())
+                    pairs = int(((hits[:-1, HN.W - 1] > 0) & (hits[1:, 0] > 0)).sum())
+                    stats.append((ties, pairs, int((hits >= 2).sum()), int(keep.sum()), int((~keep).sum())))
+                    assert ties >= 7 and pairs >= 2 and stats[-1][2] >= 100 and stats[-1][4] > 0, stats[-1]
+            pngs.append(planes)
+        out["gt_png"] = np.array(pngs)
+        # ---- _single_loss ------------------------------------------------------------------------------------------
+        rng = np.random.RandomState(31)
+        preds, losses = [], []
+        for j in range(len(HN.EVAL)):
+            for c in range(len(HN.CAMS)):
+                pred = (rng.rand(13, 21) * 30 + 0.5).astype(np.float32)
+                r = ev._single_loss(pred.copy(), (out["gt_png"][j, c] / 256.0).astype(np.float32))
+                preds.append(pred)
+                losses.append(np.concatenate([[r["ratio"]], r["error"], r["abs_error"]]).astype(np.float64))
+        out["loss_pred"], out["loss"] = np.array(preds), np.array(losses)
+        try:
+            ev._single_loss(np.ones((13, 21), np.float32), np.zeros((HN.H, HN.W), np.float32))
+            raise AssertionError("the empty valid set must raise")
+        except ValueError:
+            pass
+        # ---- FastNuscEvaluationHook with a fixed-weight model ---------------------------------------------------------
+        h, w = 64, 128
+        m = ref_model(h, w, with_pose=False)
+        m.load_state_dict(O.init_state(seed=2, with_pose=False), strict=True)
+        logged = []
+        hook = FastNuscEvaluationHook(
+            test_run_hook_cfg=dict(name='vision_base.pipeline_hooks.train_val_hooks.base_validation_hooks.BaseValidationHook'),
+            dataset_eval_cfg=dict(name='monodepth.evaluation.nuscenes_unsupervised_eval.NuscenesEvaluator',
+                                  data_path=tree["dataroot"], split_file=tree["split"], gt_saved_dir=gt_dir,
+                                  nuscenes_version=HN.VERSION),
+            batch_size=5, num_workers=0)
+        hook.dataset_eval_func.log = lambda writer, channel, me, mae, **k: logged.append((channel, me, mae))
+        vds = NusceneJsonDataset(json_path=tree["json_val"], image_keys=['frame0'], frame_ids=[0],
+                                 augmentation=HN.val_augmentation('', h, w))
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")                 # no sample of the tree is without usable points
+            hook(m, vds)
+        assert [l[0] for l in logged] == HN.CAMS + ['all mean']
+        out["hook_errors"] = np.array([l[1] for l in logged], np.float64)
+        out["hook_abs_errors"] = np.array([l[2] for l in logged], np.float64)
+        out["hook_hw"] = np.array([h, w])
+        tables = sorted(set(resolved))
+        out["resolved_tables"] = np.array([t for t, _ in tables])
+        out["resolved_tokens"] = np.array([t for _, t in tables])
+    cv2.resize = resize
+    print("nusc: %d json samples, %d tokens resolved; CAM_FRONT per sample (ties, merged edge pairs, pixels hit twice or "
+          "more, points in front, points behind): %s" % (int(out["json_n"]), len(tables), stats))
+    print("  hook all-mean errors", out["hook_errors"][-1])
+    np.savez_compressed(os.path.join(GOLD, "nusc_eval.npz"), **out)
+
+
 def gen_loss_options():
     """optional terms of MonoDepth2Decoder.loss no shipped config enables: precomputed motion_mask
     (monodepth2_decoder.py:243-246) and the pose L1 term (:176-183, 322-326), from the REAL decoder"""
@@ -1357,6 +1505,9 @@ if __name__ == "__main__":
     if "--only-kitti360" in sys.argv:
         gen_kitti360_fisheye()
         sys.exit(0)
+    if "--only-nusc" in sys.argv:
+        gen_nusc()
+        sys.exit(0)
     if "--only-kitti360-persp" in sys.argv:
         gen_kitti360_persp()
         sys.exit(0)
@@ -1386,6 +1537,7 @@ if __name__ == "__main__":
     gen_supervised_eval()
     gen_kitti360_fisheye()
     gen_kitti360_persp()
+    gen_nusc()
     gen_loss_options()
     gen_teacher_keys()
     gen_sigmoid_decoder()
