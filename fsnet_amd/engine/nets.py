@@ -763,11 +763,16 @@ class ResNetRunner:
     """One encoder's layers bound to their device plans.  Execution is EncoderPass's: forward / backward here run a
     one-lane pass; MonoDepthMeta runs the depth and the pose encoder as the two lanes of one pass."""
 
-    def __init__(self, module):
+    def __init__(self, module, first_stage=0, last_stage=None):
+        """first_stage / last_stage: run the module's stages [first_stage, last_stage) only (default: all of them).  A
+        runner that starts at stage 0 owns the stem; one that starts later is entered with the NHWC input of its first
+        stage and its backward returns the gradient with respect to that input (the matching encoder runs the stem and
+        layer1 as one pass, its cost volume and reduce_conv, then layer2-4 as another: resnet_matching.py:204-244)."""
         self.m = module
-        self.stem = ConvLayer(module.conv1, need_dgrad=False)
+        self.first_stage = first_stage
+        self.stem = ConvLayer(module.conv1, need_dgrad=False) if first_stage == 0 else None
         self.stages = []
-        for i in range(module.num_stages):
+        for i in range(first_stage, module.num_stages if last_stage is None else last_stage):
             blocks = []
             for blk in getattr(module, "layer%d" % (i + 1)):
                 if hasattr(blk, "conv3"):
@@ -792,6 +797,8 @@ class ResNetRunner:
             w = cl.m.weight
             sig.append((tuple(w.shape[2:]), w.shape[0], cl.stride, cl.pad, bool(train and bn.training), w.requires_grad,
                         bn.weight.requires_grad, bn.bias.requires_grad))
+        if self.stem is None:
+            raise NotImplementedError("a pass entered after the stem does not run as a lane")
         unit(self.stem, self.m.bn1)
         sig[0] = sig[0][:1] + ("stem",) + sig[0][2:]
         for blocks in self.stages:
@@ -814,9 +821,12 @@ class ResNetRunner:
         feats, ctx = self._solo.forward([x], train, [groups])
         return feats[0], ctx
 
-    def backward(self, ctx, gfeats):
-        """gfeats: list of 5 NHWC dense gradients (or None).  Accumulates parameter gradients."""
-        self._solo.backward(ctx, [gfeats])
+    def backward(self, ctx, gfeats, in_mask=None):
+        """gfeats: list of 5 NHWC dense gradients (or None).  Accumulates parameter gradients.  A runner entered after
+        the stem (first_stage > 0) takes one gradient per stage and returns the gradient w.r.t. its input, masked by
+        in_mask > 0 where given (the ReLU of the layer that produced the input)."""
+        g = self._solo.backward(ctx, [gfeats], in_mask=(None if in_mask is None else [in_mask]))
+        return None if g is None else g[0]
 
 
 class EncoderPass:
@@ -961,16 +971,21 @@ class EncoderPass:
         self.groups = [g if train else 1 for g in groups]
         assert all(x.shape[0] % g == 0 for x, g in zip(xs, self.groups))
         ctx = {"x": xs, "blocks": [], "train": train}
-        stem_cls, stem_bns = self._lanes(lambda r: r.stem), self._lanes(lambda r: r.m.bn1)
-        if self._stem_fusable(stem_cls, stem_bns, xs, train):
-            c0, y0, st0, pooled = self._stem_fwd_fused(stem_cls, stem_bns, xs)
-            ctx["stem_fused"] = True
+        if self.R[0].stem is None:
+            # entered after the stem: xs are the inputs of the first stage; the features are the stages' outputs
+            feats = [[] for _ in range(nl)]
+            cur = list(xs)
         else:
-            c0, y0, st0, _ = self._unit_fwd(stem_cls, stem_bns, xs, train)
-            pooled = ops.maxpool_fwd_multi(y0)
-        ctx.update(c0=c0, y0=y0, st0=st0, idx=[p[1] for p in pooled])
-        feats = [[y] for y in y0]
-        cur = [p[0] for p in pooled]
+            stem_cls, stem_bns = self._lanes(lambda r: r.stem), self._lanes(lambda r: r.m.bn1)
+            if self._stem_fusable(stem_cls, stem_bns, xs, train):
+                c0, y0, st0, pooled = self._stem_fwd_fused(stem_cls, stem_bns, xs)
+                ctx["stem_fused"] = True
+            else:
+                c0, y0, st0, _ = self._unit_fwd(stem_cls, stem_bns, xs, train)
+                pooled = ops.maxpool_fwd_multi(y0)
+            ctx.update(c0=c0, y0=y0, st0=st0, idx=[p[1] for p in pooled])
+            feats = [[y] for y in y0]
+            cur = [p[0] for p in pooled]
         for si in range(len(self.R[0].stages)):
             for bi in range(len(self.R[0].stages[si])):
                 units = [r.stages[si][bi][0] for r in self.R]          # per lane: [(ConvLayer, bn)]
@@ -1070,11 +1085,13 @@ class EncoderPass:
     def _param_grads(self, cls, ops_, dcs, xs, pros=None):
         accumulate_param_grads_multi(cls, ops_, dcs, xs, pros if pros is not None else [None] * self.nl)
 
-    def _block_bwd(self, units, ds, bctx, dout, extra, dout_sums=None, prev=None):
+    def _block_bwd(self, units, ds, bctx, dout, extra, dout_sums=None, prev=None, in_mask=None):
         """dout: gradient w.r.t. the block output.  dout_sums: set when dout came out of a data-gradient epilogue
         that already masked it with this block's output ReLU and accumulated the BatchNorm-backward sums.
         prev = (y, c, BnState) of the block that consumes the returned gradient (fused the same way).
         units: per lane [(ConvLayer, bn)], ds: per lane (ConvLayer, bn) or None; every tensor argument is a per-lane list.
+        in_mask (without prev): the returned gradient is masked by in_mask > 0 — the ReLU of a producer that is not a
+        block of this pass (the first block of a pass entered after the stem).
 """
         nl = self.nl
         x = bctx["x"]
@@ -1181,22 +1198,28 @@ class EncoderPass:
             sums = self._sums(pc, pst)
             out = self._dgrad(op, src, hw_x, [dict(addend=dres[l], mask=py[l], bn_fuse=(pc[l], pst[l], sums[l]), **kw[l])
                                                for l in range(nl)]), sums
+        elif in_mask is not None:
+            out = self._dgrad(op, src, hw_x, [dict(addend=dres[l], mask=in_mask[l], **kw[l]) for l in range(nl)]), None
         else:
             out = self._dgrad(op, src, hw_x, [dict(addend=dres[l], **kw[l]) for l in range(nl)]), None
         self._param_grads(cls, op, dc, x)
         return out
 
-    def backward(self, ctx, gfeats):
-        """gfeats: per lane a list of 5 NHWC dense gradients (or None).  Accumulates parameter gradients."""
+    def backward(self, ctx, gfeats, in_mask=None):
+        """gfeats: per lane a list of 5 NHWC dense gradients (or None).  Accumulates parameter gradients.
+        A pass entered after the stem: gfeats has one entry per stage (the features that pass returned), and the result is
+        the per-lane gradient w.r.t. the pass's input, masked by in_mask[l] > 0 where in_mask is given."""
         nl = self.nl
         R0 = self.R[0]
         nst = len(R0.stages)
+        entered = R0.stem is None
+        fo = 0 if entered else 1               # features[0] is the stem's activation unless the pass has no stem
         xs = ctx["x"]
         bwd_pool_reset(xs[0].device)
         tag = "enc%d" % sum(x.shape[0] for x in xs)
         RT.mark(tag + ".bwd.start")
         last = ctx["blocks"][-1]["u"][-1][2]
-        dout = [gfeats[l][nst] if gfeats[l][nst] is not None else torch.zeros_like(last[l]) for l in range(nl)]
+        dout = [gfeats[l][nst - 1 + fo] if gfeats[l][nst - 1 + fo] is not None else torch.zeros_like(last[l]) for l in range(nl)]
         bi = len(ctx["blocks"])
         dsums = None
         for si in range(nst - 1, -1, -1):
@@ -1208,21 +1231,25 @@ class EncoderPass:
                 dss = [r.stages[si][b][1] for r in self.R]
                 ds = None if dss[0] is None else dss
                 extra = None
-                if b == 0 and si > 0 and any(gfeats[l][si] is not None for l in range(nl)):
+                if b == 0 and si > 0 and any(gfeats[l][si - 1 + fo] is not None for l in range(nl)):
                     if ds is None:
                         raise NotImplementedError("feature gradient into a block without downsample")
                     # (per lane: one lane's decoder reads this feature, the other's does not — the pose decoder only takes
                     # the last one; the shared launch's epilogue options are per problem)
-                    extra = [gfeats[l][si] for l in range(nl)]
+                    extra = [gfeats[l][si - 1 + fo] for l in range(nl)]
                 prev = None
-                if bi > 0 and not (b == 0 and any(gfeats[l][si] is not None for l in range(nl)) and ds is None):
+                if bi > 0 and not (b == 0 and any(gfeats[l][si - 1 + fo] is not None for l in range(nl)) and ds is None):
                     pu = ctx["blocks"][bi - 1]["u"][-1]
                     # the consumer of the returned gradient is the previous block's output BatchNorm, unless a
                     # feature gradient still has to be added to it first (stage boundary without downsample)
                     prev = (pu[2], pu[1], pu[3])
                 issue_advanced(xs[0].device)
+                if entered and bi == 0:
+                    dout, dsums = self._block_bwd(units, ds, ctx["blocks"][bi], dout, extra, dout_sums=dsums, prev=None,
+                                                  in_mask=in_mask)
+                    continue
                 dout, dsums = self._block_bwd(units, ds, ctx["blocks"][bi], dout, extra, dout_sums=dsums, prev=prev)
-            if RT.dp is not None and si >= 2:
+            if RT.dp is not None and si + R0.first_stage >= 2:
                 for r in self.R:
                     if r.m._pending == 1:
                         # (only the module's LAST pending backward of the step: an encoder that ran several training forwards —
@@ -1230,7 +1257,13 @@ class EncoderPass:
                         # reduced after the first backward would be reduced again with the second one's local sums on top)
                         # gradient bucket of this stage (reverse parameter order, like DDP): layer4 and layer3 carry 94 % of
                         # the encoder's parameters and finish first
-                        RT.dp.partial_ready(r.m, [getattr(r.m, "layer%d" % (si + 1))])
+                        RT.dp.partial_ready(r.m, [getattr(r.m, "layer%d" % (si + 1 + R0.first_stage))])
+        if entered:
+            RT.mark(tag + ".bwd.end")
+            flush_deferred(_current_stream())
+            _ENCODER_END[0] = False
+            chain_ends(xs[0].device)
+            return dout
         y0 = ctx["y0"]
         add0 = [gfeats[l][0] for l in range(nl)]
         if RT.stem_flush:

@@ -1162,3 +1162,49 @@ def distill_bwd(pred, teacher, uncertain, gout):
     check(lib.fs_distill_bwd(pred.data_ptr(), teacher.data_ptr(), _p(uncertain), pred.numel(), _p(gout), d_pred.data_ptr(),
                              _p(d_unc), stream_ptr()), "distill_bwd")
     return d_pred, d_unc
+
+
+COST_VOLUME_MAX_BINS = 128
+
+
+def cost_volume(cur, look, K, inv_K, poses, bins, cat, want_volume=False):
+    """Plane-sweep matching cost volume of a whole batch in one launch (fs_cost_volume; resnet_matching.py:83-173, 227-237).
+    cur [B,h,w,C] and look [B*F,h,w,C]: NHWC features in the compute dtype; K, inv_K [B,4,4], poses [B,F,4,4], bins [D]:
+    fp32 on the device; cat [B,h,w,Ci_p] in the compute dtype: channels [C, C+D) receive cost * confidence, the padding
+    channels behind them zero, channels [0, C) stay as they are.
+    -> (confidence [B,h,w], lowest_cost [B,h,w]) fp32, and with want_volume the filled, unmasked fp32 cost volume and the
+    missing mask, both [B,D,h,w].  No host sync."""
+    if cur.dim() != 4 or look.dim() != 4 or cat.dim() != 4 or poses.dim() != 4 or bins.dim() != 1:
+        raise ValueError("cost_volume: cur / look / cat are NHWC, poses [B,F,4,4], bins [D]")
+    B, h, w, Cc = cur.shape
+    F, D = poses.shape[1], bins.shape[0]
+    if Cc < 16 or Cc % 16:
+        raise ValueError("cost_volume: the feature width must be a positive multiple of 16, got %d" % Cc)
+    if not 1 <= D <= COST_VOLUME_MAX_BINS:
+        raise ValueError("cost_volume: 1 <= depth bins <= %d, got %d" % (COST_VOLUME_MAX_BINS, D))
+    if F < 1 or h < 5 or w < 5:
+        raise ValueError("cost_volume: needs F >= 1 and h, w >= 5, got F=%d h=%d w=%d" % (F, h, w))
+    if cur.dtype not in (torch.float32, torch.bfloat16) or look.dtype != cur.dtype or cat.dtype != cur.dtype:
+        raise ValueError("cost_volume: cur, look and cat share one compute dtype (fp32 or bf16)")
+    if tuple(look.shape) != (B * F, h, w, Cc) or tuple(poses.shape) != (B, F, 4, 4) or tuple(K.shape) != (B, 4, 4) \
+            or tuple(inv_K.shape) != (B, 4, 4) or tuple(cat.shape[:3]) != (B, h, w) or cat.shape[3] < Cc + D:
+        raise ValueError("cost_volume: shapes disagree (cur %s look %s poses %s K %s inv_K %s cat %s)" % (
+            tuple(cur.shape), tuple(look.shape), tuple(poses.shape), tuple(K.shape), tuple(inv_K.shape), tuple(cat.shape)))
+    for name, t in (("K", K), ("inv_K", inv_K), ("poses", poses), ("bins", bins)):
+        if t.dtype != torch.float32 or t.device != cur.device or not t.is_contiguous():
+            raise ValueError("cost_volume: %s must be a contiguous fp32 tensor on the features' device" % name)
+    if not (cur.is_contiguous() and look.is_contiguous() and cat.is_contiguous()):
+        raise ValueError("cost_volume: cur, look and cat must be dense NHWC")
+    if B * h * w >= 1 << 31 or h * w * Cc >= 1 << 31:
+        raise ValueError("cost_volume: B*h*w and h*w*C must stay below 2^31")
+    dev = cur.device
+    conf = torch.empty(B, h, w, dtype=torch.float32, device=dev)
+    lowest = torch.empty(B, h, w, dtype=torch.float32, device=dev)
+    vol = torch.empty(B, D, h, w, dtype=torch.float32, device=dev) if want_volume else None
+    miss = torch.empty(B, D, h, w, dtype=torch.float32, device=dev) if want_volume else None
+    check(lib.fs_cost_volume(cur.data_ptr(), look.data_ptr(), K.data_ptr(), inv_K.data_ptr(), poses.data_ptr(),
+                             bins.data_ptr(), cat.data_ptr(), conf.data_ptr(), lowest.data_ptr(), _p(vol), _p(miss),
+                             B, F, h, w, Cc, D, cat.shape[3], dtype_code(cur.dtype), stream_ptr()), "cost_volume")
+    if want_volume:
+        return conf, lowest, vol, miss
+    return conf, lowest

@@ -55,6 +55,8 @@ SIGNATURES = {
     "fs_depth_errors9": (C.c_int, [P, P, I, I, D, I, I, I, P, L, P, P]),
     "fs_depth_errors9_workspace_bytes": (C.c_int64, [I, I, I]),
     "fs_depth_quantize_u16": (C.c_int, [P, P, F, I, I, P]),
+    # added under ABI 15: ResnetEncoderMatching.match_features + confidence / lowest cost (resnet_matching.py:83-173, 227-237)
+    "fs_cost_volume": (C.c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "fs_postopt": (C.c_int, [P, P]),
     "fs_postopt_workspace_bytes": (C.c_int64, [I, I, I, I]),
     "fs_optflow_farneback": (C.c_int, [P, P]),

@@ -508,6 +508,26 @@ int fs_copy_multi(const void* const* src, void* const* dst, const int64_t* bytes
  * (base_training_hooks.py:34 optimizer.zero_grad() is the reference's only such call: the rest is engine scratch). */
 int fs_zero_multi(void* const* dst, const int64_t* bytes, int n, void* stream);
 
+/* Plane-sweep matching cost volume of the multi-frame encoder (added under ABI 15): ResnetEncoderMatching.match_features
+ * and the confidence / lowest-cost / masking lines of its forward (resnet_matching.py:83-173, 227-237) in ONE launch for
+ * the whole batch; the warped [D][C][h][w] features never reach memory.
+ * cur [B][h][w][C] and look [B*F][h][w][C]: NHWC features in the compute dtype (16-byte aligned); K, inv_K [B][4][4],
+ * poses [B][F][4][4], bins [D]: device fp32.  Per current pixel, depth bin and lookup frame, in fp32 and the reference's
+ * order: point = bin * inv_K[:3,:3] (x, y, 1); p = (K T)[:3,:] (point, 1); pixel = p.xy / (p.z + 1e-7) (no sign test);
+ * normalised with /(w-1), /(h-1), (. - 0.5) * 2; bilinear sample, align_corners, zeros padding; the sample counts iff
+ * 2 <= x <= w-2 and 2 <= y <= h-2 on (. / 2 + 0.5) * (w-1 | h-1) and the current pixel lies in [2:-2, 2:-2]; cost +=
+ * mean_C |warped - current|, count += (that mean > 0).  A frame whose 16 pose entries sum to exactly 0 is skipped (on
+ * the device: no host sync, capturable).  Then cost / (count + 1e-7); missing = (cost == 0); missing bins take the
+ * pixel's maximum over the bins; confidence [B][h][w] = 1 where no bin is missing; lowest [B][h][w] = 1 / bins[first
+ * argmin over the filled costs with exact zeros read as 100].
+ * cat [B][h][w][Ci_p] (compute dtype): channels [C, C+D) receive cost * confidence, channels [C+D, Ci_p) zero, channels
+ * [0, C) are not touched.  cost_f32 / missing (both or neither; [B][D][h][w] fp32): the filled, unmasked costs and the
+ * missing mask.  FS_EINVAL: C not a positive multiple of 16, D outside 1..128, F < 1, h or w < 5, Ci_p < C + D,
+ * B*h*w or h*w*C >= 2^31. */
+int fs_cost_volume(const void* cur, const void* look, const float* K, const float* inv_K, const float* poses,
+                   const float* bins, void* cat, float* confidence, float* lowest, float* cost_f32, float* missing,
+                   int B, int F, int h, int w, int C, int D, int Ci_p, int dtype, void* stream);
+
 /* Batch images NCHW fp32 (one tensor, or two concatenated along C as the pose encoder input,
  * monodepth2_model.py:29-35) -> NHWC with Cp >= Ca+Cb zero-padded channels.
  */
