@@ -162,3 +162,42 @@ __device__ __forceinline__ float tie_noise(int seed, uint32_t key) {
 }
 
 }  // namespace
+
+// The helpers below are inlined into kernels of files with different contraction modes, and `#pragma clang fp` is
+// lexical: a helper defined under the library's -ffp-contract=off keeps its adds unfused wherever it lands.  A file that
+// allows FMAs (photo_fused.hip) defines FS_PHOTO_CONTRACT_FAST before including this header, so that the helpers are
+// compiled exactly as when they were defined below its own pragma; everything above stays unfused for it as before
+// (which is why that file cannot simply put its pragma in front of the include: the geometry helpers above would then
+// contract in its fisheye kernels).  A file-scope pragma has no end: it stays in force after this header for the rest of
+// the translation unit, so such a file includes this header last, and repeats the pragma where its own code begins.
+#ifdef FS_PHOTO_CONTRACT_FAST
+#pragma clang fp contract(fast)
+#endif
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------
+// row-walking strips (photo_fused.hip, the identity kernel of photometric.hip): lane l of a wave holds column
+// x0 - 1 + l of the strip, lanes 0 and 63 are halo
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float hsum3(float v) {
+  // lane i: v[i-1] + v[i] + v[i+1] (wave-wide shifts; the missing neighbour of lanes 0 / 63 reads 0: halo lanes)
+  return (dpp_mov<0x138>(v) + v) + dpp_mov<0x130>(v);
+}
+
+// Two source frames per lane as one 2-vector: everything a frame owns — projection, sampler weights, the SSIM terms —
+// is the same arithmetic on two independent values, and gfx950 issues v_pk_fma / v_pk_mul / v_pk_add_f32 on a register
+// pair at the rate of the scalar forms (round 6; what has no packed form — v_rcp, min / max, floor, the DPP row sums —
+// runs per component).  The compiler's own SLP packing of the scalar code had been measured slower (register shuffles
+// to build the pairs: hence -fno-slp-vectorize in photo_fused.hip); here the pairs are the data layout.
+typedef float f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f2 splat(float v) { return f2{v, v}; }
+__device__ __forceinline__ f2 hsum3(f2 v) { return f2{hsum3(v.x), hsum3(v.y)}; }
+
+// load base[byte_off / 4] with a 32-bit byte offset: lets the compiler keep the (uniform) base in SGPRs and address
+// with one VGPR (global_load ... s[base]) instead of a 64-bit add per load
+__device__ __forceinline__ float ldg(const float* base, unsigned byte_off) {
+  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+
+}  // namespace

@@ -14,8 +14,11 @@
 // stretch), the four scales of a strip run back to back on the same XCD, so the source rows stay cache resident.
 // FS_HIPCC_FLAGS: -fno-slp-vectorize
 // (SLP packing into v_pk_add/mul_f32 costs register shuffles here and keeps the DPP shifts from folding into the adds)
-#include "photo_common.h"
 #include <algorithm>
+// photo_common.h's row helpers (hsum3, f2, ldg) under this file's contraction mode: the header switches it on in front of
+// them and it stays on from there — last include, so that it reaches nothing but this file's own code
+#define FS_PHOTO_CONTRACT_FAST
+#include "photo_common.h"
 
 // fused multiply-adds allowed in this file (the library builds with -ffp-contract=off to mirror the unfused ATen
 // arithmetic of the staged kernels; here an FMA only removes a rounding and a third of the VALU instructions)
@@ -26,19 +29,8 @@ namespace {
 constexpr int FW = 62;    // output columns per wave (lanes 1..62; lanes 0 and 63 are halo)
 constexpr int FRH = 16;   // output rows per wave
 
-__device__ __forceinline__ float hsum3(float v) {
-  // lane i: v[i-1] + v[i] + v[i+1] (wave-wide shifts; the missing neighbour of lanes 0 / 63 reads 0: halo lanes)
-  return (dpp_mov<0x138>(v) + v) + dpp_mov<0x130>(v);
-}
-
-// Two source frames per lane as one 2-vector: everything a frame owns — projection, sampler weights, the SSIM terms —
-// is the same arithmetic on two independent values, and gfx950 issues v_pk_fma / v_pk_mul / v_pk_add_f32 on a register
-// pair at the rate of the scalar forms (round 6; what has no packed form — v_rcp, min / max, floor, the DPP row sums —
-// runs per component).  The compiler's own SLP packing of the scalar code had been measured slower (register shuffles
-// to build the pairs: hence -fno-slp-vectorize above); here the pairs are the data layout.
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 splat(float v) { return f2{v, v}; }
-__device__ __forceinline__ f2 hsum3(f2 v) { return f2{hsum3(v.x), hsum3(v.y)}; }
+// (hsum3, the per-lane frame pair f2 and the row load ldg live at the end of photo_common.h: the identity kernel of
+// photometric.hip walks rows the same way)
 
 // The three colour channels of one quantity as a packed pair + a scalar (backward kernel: a wave owns ONE frame there, the
 // channels are what is independent): two instructions where three scalar ones stood, no register overhead.
@@ -70,11 +62,6 @@ struct Row {       // one image row of a strip: horizontal 3-tap sums + the raw 
   bool ov[2];
 };
 
-// load base[byte_off / 4] with a 32-bit byte offset: lets the compiler keep the (uniform) base in SGPRs and address
-// with one VGPR (global_load ... s[base]) instead of a 64-bit add per load
-__device__ __forceinline__ float ldg(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 // two horizontally adjacent texels in ONE 8-byte load at 4-byte alignment (global memory runs in unaligned access
 // mode on gfx9): the gather is bound by the number of vector-memory instructions, not by their bytes
 struct __attribute__((packed, aligned(4))) F2u { float a, b; };

@@ -9,6 +9,9 @@
 //   compute_total_reprojection_loss (min / masks)     monodepth2_decoder.py:205-292
 // All four scales run in ONE launch per stage (every stage works at full resolution; only the
 // low-res depth map differs).  Images stay planar NCHW fp32 exactly as the data layer hands them over.
+// FS_HIPCC_FLAGS: -fno-slp-vectorize
+// (as in photo_fused.hip: SLP packing of the row-walking identity kernel's window sums turns each DPP add into a DPP move
+// plus a packed add, costs 12 VGPRs — one wave per SIMD of occupancy — and parks a row's raw values in LDS)
 #include "photo_common.h"
 #include <algorithm>
 
@@ -84,9 +87,12 @@ __device__ __forceinline__ float reproj_at(const float* __restrict__ xp, const f
 
 // One block = a 64 x 4 pixel tile of one sample: the nine planes (target + two source frames, three channels each)
 // are staged ONCE with their reflected one-pixel halo into LDS and both identity terms read their 3x3 windows from
-// there, in the same order and with the same arithmetic as reproj_at() above (bit-identical results).  The first
-// version gathered 108 values per pixel from global memory (the target window twice): 154 us per step — as long as
-// the whole fused forward of all four scales — for 65 MB of input.
+// there, in the same order and with the same arithmetic as reproj_at() above (bit-identical results).  History: the
+// first version gathered 108 values per pixel from global memory (the target window twice), 154 us per step for 65 MB
+// of input; this tile form took 91 us (1.55x the pixels fetched for the halo, 4-byte staging loads behind two integer
+// divisions, 108 LDS reads per pixel, the target's window sums once per frame).  The training step now calls the
+// row-walking kernel below (fs_photo_identity_rows); fs_photo_identity stays exported as the reference-order form the
+// tests measure the new one against.
 constexpr int ID_TW = 64, ID_TH = 4, ID_HW = ID_TW + 2, ID_HH = ID_TH + 2;
 
 __global__ __launch_bounds__(256) void photo_ident_kernel(const FsPhotoArgs p) {
@@ -139,6 +145,125 @@ __global__ __launch_bounds__(256) void photo_ident_kernel(const FsPhotoArgs p) {
   __shared__ double sh[4];
   msum = block_sum_d(msum, sh);
   if (threadIdx.x == 0) atomicAdd(p.mask_sum + b, msum);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same two planes by walking rows (the decomposition of photo_fused_fwd_kernel): a wave owns a strip of 62 columns x
+// ID_RS rows of one sample, lane l holds column x0 - 1 + l (lanes 0 and 63 are halo), the horizontal 3-tap sums are two
+// DPP adds, the last two rows' sums stay in registers and the vertical sum is two adds: no LDS, every plane is read once
+// apart from the halo, and the target's window sums are formed once for both frames.  Reflection padding = the halo
+// lane / halo row loads the reflected pixel.  The nine taps are added as (row sums of three) of three instead of one
+// after the other, so a value may differ from reproj_at()'s in the last bits; after the sums it is the same unfused
+// arithmetic except for the quotient (div_nr) and the two means over the channels (x 1/3), with sigma_x, sigma_t and
+// sigma_xt in one expression shape: a frame equal to the target still gives exactly 0.  The next row's loads are
+// issued into the ring slot whose raw values are no longer needed before the current row is worked on.
+// Strip height: a strip re-reads (and re-sums) 2 halo rows, so ID_RS = 16 costs 12.5 % more rows than the image has
+// (8: 25 %, 32: 6 %).  Measured alone at 192x640 / batch 12 and 384x384 / batch 16, inputs from HBM: 8 rows 43.8 /
+// 68.6 us, 12: 38.6 / 53.4, 16: 35.1 / 45.9, 24: 40.7 / 47.0, 32: 37.4 / 51.0 (the tile kernel: 90.9 / 134.7) — the
+// 1.5 waves per SIMD of 16 rows hide a row's loads well enough behind the row before it.  (Taken with IEEE quotients;
+// div_nr below then brought 16 rows to 32.7 / 42.6 us.  docs/LAB_r07.md.)
+// ---------------------------------------------------------------------------------------------
+constexpr int ID_W = 62;              // output columns per wave (lanes 1..62)
+constexpr int ID_RS = 16;             // output rows per wave
+
+// n / d without the scaling steps of the IEEE sequence (ten instructions, a third of the kernel's arithmetic with the
+// six quotients of a pixel): v_rcp_f32 (1 ulp) and one Newton step on the quotient with the exact fma remainder.  Within
+// 1 ulp of n / d, and exactly 1 for n == d (q = 1 + e, the remainder -d e is exact, q - d e r rounds to 1), which the
+// exact zero of equal frames rests on.  d = (mu_x^2 + mu_t^2 + C1)(sigma_x + sigma_t + C2) is neither denormal nor huge.
+__device__ __forceinline__ float div_nr(float n, float d) {
+  const float r = __builtin_amdgcn_rcpf(d);
+  const float q = n * r;
+  return __builtin_fmaf(__builtin_fmaf(-d, q, n), r, q);
+}
+
+struct IdRow {
+  float rt[3];                        // raw target values, per channel
+  f2 rx[3];                           // raw source values (component = source frame)
+  float t[3], tt[3];                  // horizontal 3-tap sums
+  f2 x[3], xx[3], xt[3];
+};
+
+__global__ __launch_bounds__(256) void photo_ident_rows_kernel(const FsPhotoArgs p, int SX, int SY, int nwaves) {
+  const int wv = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + ((int)threadIdx.x >> 6));
+  if (wv >= nwaves) return;
+  const int lane = threadIdx.x & 63;
+  const int sx = wv % SX;
+  const int rest = wv / SX;
+  const int sy = rest % SY, b = rest / SY;
+  const int H = p.H, W = p.W;
+  const unsigned HW = (unsigned)(H * W);
+  const float* timg = p.img0 + (long)b * 3 * HW;
+  const float* src0 = p.img_src[0] + (long)b * 3 * HW;
+  const float* src1 = p.img_src[1] + (long)b * 3 * HW;
+  float* out = p.ident + (long)b * 2 * HW;
+  const double* pm = p.patched_mask ? p.patched_mask + (long)b * HW : nullptr;
+  const int x = sx * ID_W - 1 + lane;
+  const int xr = min(max(refl(x, W), 0), W - 1);     // (columns past the halo only feed lanes that are not written)
+  const bool col_out = lane >= 1 && lane <= ID_W && x < W;
+  const int ys = sy * ID_RS;
+  const int nsteps = min(ID_RS, H - ys) + 2;         // rows ys - 1 .. ys + rows of the strip
+  double msum = 0.0;
+
+  auto load = [&](IdRow& r, const int it) {
+    const int yr = min(max(refl(ys - 1 + it, H), 0), H - 1);
+    const unsigned ob = (unsigned)(yr * W + xr) * 4u;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      r.rt[c] = ldg(timg + c * HW, ob);
+      r.rx[c] = f2{ldg(src0 + c * HW, ob), ldg(src1 + c * HW, ob)};
+    }
+  };
+
+  // one row: `r0` holds the raw values of row y = ys - 1 + it; from the third row on, finish the window centred on `r1`
+  auto step = [&](IdRow& r2, const IdRow& r1, IdRow& r0, const int it) {
+    load(r2, min(it + 1, nsteps - 1));               // next row (this step reads r2's sums only); last step: a re-load, unused
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      r0.t[c] = hsum3(r0.rt[c]);
+      r0.tt[c] = hsum3(r0.rt[c] * r0.rt[c]);
+      r0.x[c] = hsum3(r0.rx[c]);
+      r0.xx[c] = hsum3(r0.rx[c] * r0.rx[c]);
+      r0.xt[c] = hsum3(r0.rx[c] * r0.rt[c]);
+    }
+    if (it < 2) return;
+    const int yc = ys + it - 2;                      // < H by nsteps
+    const float k = 1.f / 9.f;
+    f2 ssim_sum = splat(0.f), l1 = splat(0.f);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float sy_ = (r2.t[c] + r1.t[c]) + r0.t[c], syy = (r2.tt[c] + r1.tt[c]) + r0.tt[c];
+      const f2 sxs = (r2.x[c] + r1.x[c]) + r0.x[c], sxx = (r2.xx[c] + r1.xx[c]) + r0.xx[c],
+               sxy = (r2.xt[c] + r1.xt[c]) + r0.xt[c];
+      const float muy = sy_ * k;
+      const f2 mux = sxs * k;
+      const float sgy = syy * k - muy * muy;
+      const f2 sgx = sxx * k - mux * mux, sgxy = sxy * k - mux * muy;
+      const f2 n = (2.f * mux * muy + C1) * (2.f * sgxy + C2);
+      const f2 d = (mux * mux + muy * muy + C1) * (sgx + sgy + C2);
+      const f2 sv = (1.f - f2{div_nr(n.x, d.x), div_nr(n.y, d.y)}) * 0.5f;
+      ssim_sum += f2{fminf(fmaxf(sv.x, 0.f), 1.f), fminf(fmaxf(sv.y, 0.f), 1.f)};
+      const f2 df = r1.rt[c] - r1.rx[c];
+      l1 += f2{fabsf(df.x), fabsf(df.y)};
+    }
+    if (col_out) {
+      const float k3 = 1.f / 3.f;                    // (the tile kernel divides by 3: at most one more ulp here)
+      const f2 v = 0.85f * (ssim_sum * k3) + 0.15f * (l1 * k3);
+      const unsigned i = (unsigned)(yc * W + x);
+      out[i] = v.x;
+      out[HW + i] = v.y;
+      msum += pm ? pm[i] : 1.0;
+    }
+  };
+
+  IdRow A, B, C;
+  load(A, 0);
+  for (int it = 0; it < nsteps; it += 3) {           // (nsteps >= 3; the row ring is rotated by unrolling three steps)
+    step(B, C, A, it);
+    if (it + 1 < nsteps) step(C, A, B, it + 1);
+    if (it + 2 < nsteps) step(A, B, C, it + 2);
+  }
+  msum = wave_sum_d(msum);                           // mask values are 0 / 1: the f64 sum is exact in any order
+  if (lane == 0) atomicAdd(p.mask_sum + b, msum);
 }
 
 // (Rounds 1-2 ran the chain as three staged kernels here — warp to HBM, loss forward, loss backward; the fused kernels of
@@ -208,6 +333,20 @@ extern "C" int fs_photo_identity(const FsPhotoArgs* a, void* stream) {
   hipLaunchKernelGGL(photo_ident_kernel, grid, dim3(256), 0, st, *a);
   return fs_launch_status();
 }
+
+extern "C" int fs_photo_identity_rows(const FsPhotoArgs* a, void* stream) {
+  if (!valid(a) || !a->ident || !a->mask_sum) return FS_EINVAL;
+  if ((long)a->H * a->W * 3 >= 0x40000000L) return FS_EINVAL;          // 32-bit plane offsets
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int SX = (a->W + ID_W - 1) / ID_W, SY = (a->H + ID_RS - 1) / ID_RS;
+  const long nwaves = (long)a->B * SY * SX;
+  const long nblk = (nwaves + 3) / 4;
+  if (nwaves > 0x7ffffff0L) return FS_EINVAL;
+  hipLaunchKernelGGL(photo_ident_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, st, *a, SX, SY, (int)nwaves);
+  return fs_launch_status();
+}
+
+extern "C" int fs_photo_identity_strip_rows(void) { return ID_RS; }
 
 extern "C" int fs_photo_pose_grad(const float* geo, const float* dP, float* dT0, float* dT1, int B, int S, int tiles,
                                   void* stream) {

@@ -26,6 +26,46 @@ __global__ __launch_bounds__(256) void color_pyramid_kernel(const float* __restr
   }
 }
 
+// The three standard levels (ratios 2, 4 and 8) from ONE read of the image: a thread owns one 8x8 cell of one plane, loads
+// its eight rows as 16-byte units (neighbouring lanes are 32 bytes apart: the two loads of a row use every fetched
+// line in full) and keeps each level's block sums in the order of color_pyramid_kernel — row-major within the level's
+// own block, one division at the end — so the outputs are bit-identical to three launches of that kernel, which read
+// the image three times with 4-byte loads up to 32 bytes apart.
+__global__ __launch_bounds__(64) void color_pyramid3_kernel(const float* __restrict__ img, float* __restrict__ o2,
+                                                            float* __restrict__ o4, float* __restrict__ o8,
+                                                            long cells, int H, int W) {
+  const long i = (long)blockIdx.x * 64 + threadIdx.x;
+  if (i >= cells) return;
+  const int cw = W >> 3, ch = H >> 3;
+  const int cx = (int)(i % cw);
+  const long q = i / cw;
+  const int cy = (int)(q % ch);
+  const long bc = q / ch;
+  const float* src = img + bc * H * W + (long)(cy * 8) * W + cx * 8;
+  float4 v[8][2];
+#pragma unroll
+  for (int a = 0; a < 8; ++a) {
+    v[a][0] = *reinterpret_cast<const float4*>(src + (long)a * W);
+    v[a][1] = *reinterpret_cast<const float4*>(src + (long)a * W + 4);
+  }
+  float* d2 = o2 + bc * (H >> 1) * (W >> 1) + (long)(cy * 4) * (W >> 1) + cx * 4;
+  float* d4 = o4 + bc * (H >> 2) * (W >> 2) + (long)(cy * 2) * (W >> 2) + cx * 2;
+  float s2[4], s4[2], s8 = 0.f;
+#pragma unroll
+  for (int a = 0; a < 8; ++a) {
+    const float e[8] = {v[a][0].x, v[a][0].y, v[a][0].z, v[a][0].w, v[a][1].x, v[a][1].y, v[a][1].z, v[a][1].w};
+    if (a % 2 == 0) s2[0] = s2[1] = s2[2] = s2[3] = 0.f;
+    if (a % 4 == 0) s4[0] = s4[1] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { s2[c >> 1] += e[c]; s4[c >> 2] += e[c]; s8 += e[c]; }
+    if (a % 2 == 1)
+      *reinterpret_cast<float4*>(d2 + (long)(a >> 1) * (W >> 1)) =
+          make_float4(s2[0] / 4.f, s2[1] / 4.f, s2[2] / 4.f, s2[3] / 4.f);
+    if (a % 4 == 3) *reinterpret_cast<float2*>(d4 + (long)(a >> 2) * (W >> 2)) = make_float2(s4[0] / 16.f, s4[1] / 16.f);
+  }
+  o8[i] = s8 / 64.f;
+}
+
 // per (scale, batch) sum of disp -> sums[s][b]  (mean = sums / (h*w))
 __global__ __launch_bounds__(256) void smooth_mean_kernel(const FsSmoothArgs p) {
   const int s = blockIdx.z, b = blockIdx.y;
@@ -209,11 +249,40 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 
 }  // namespace
 
-extern "C" int fs_color_pyramid(const float* img, float* out, int B, int H, int W, int h, int w, void* stream) {
-  if (!img || !out || h <= 0 || w <= 0 || H % h != 0 || W % w != 0) return FS_EINVAL;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+static void launch_pyramid_level(const float* img, float* out, int B, int H, int W, int h, int w, hipStream_t st) {
   long total = (long)B * 3 * h * w;
   hipLaunchKernelGGL(color_pyramid_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, img, out, B, H, W, h, w);
+}
+
+extern "C" int fs_color_pyramid(const float* img, float* out, int B, int H, int W, int h, int w, void* stream) {
+  if (!img || !out || h <= 0 || w <= 0 || H % h != 0 || W % w != 0) return FS_EINVAL;
+  launch_pyramid_level(img, out, B, H, W, h, w, reinterpret_cast<hipStream_t>(stream));
+  return fs_launch_status();
+}
+
+extern "C" int fs_color_pyramid_multi(const float* img, float* const* outs, const int32_t* hs, const int32_t* ws, int n,
+                                      int B, int H, int W, void* stream) {
+  if (!img || !outs || !hs || !ws || n < 1 || n > 4 || B < 1 || H < 1 || W < 1) return FS_EINVAL;
+  for (int i = 0; i < n; ++i)
+    if (!outs[i] || hs[i] <= 0 || ws[i] <= 0 || H % hs[i] != 0 || W % ws[i] != 0) return FS_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // the one-read kernel: exactly the ratios 2, 4 and 8 (any order) of an image whose sides are multiples of 8
+  float* lv[4] = {nullptr, nullptr, nullptr, nullptr};      // by log2(ratio)
+  bool fast = n == 3 && H % 8 == 0 && W % 8 == 0 && ((uintptr_t)img & 15) == 0;
+  for (int i = 0; fast && i < n; ++i) {
+    const int ry = H / hs[i], rx = W / ws[i];
+    const int l = ry == 2 ? 1 : (ry == 4 ? 2 : (ry == 8 ? 3 : 0));
+    if (ry != rx || l == 0 || lv[l] || ((uintptr_t)outs[i] & 15) != 0) fast = false;
+    else lv[l] = outs[i];
+  }
+  if (fast) {
+    const long cells = (long)B * 3 * (H / 8) * (W / 8);
+    if ((cells + 63) / 64 > 0x7fffffffL) return FS_EINVAL;
+    hipLaunchKernelGGL(color_pyramid3_kernel, dim3((unsigned)((cells + 63) / 64)), dim3(64), 0, st, img, lv[1], lv[2],
+                       lv[3], cells, H, W);
+  } else {
+    for (int i = 0; i < n; ++i) launch_pyramid_level(img, outs[i], B, H, W, hs[i], ws[i], st);
+  }
   return fs_launch_status();
 }
 

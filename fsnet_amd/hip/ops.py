@@ -456,6 +456,12 @@ class PhotometricLoss:
         self.dT = [torch.zeros(B, 4, 4, dtype=f32, device=device) for _ in range(2)]
         self.pyr = [None if s == 0 else torch.empty(B, 3, H >> s, W >> s, dtype=f32, device=device)
                     for s in self.scales]
+        # the levels below full resolution as host arrays for fs_color_pyramid_multi (the buffers are persistent)
+        lv = [i for i, s in enumerate(self.scales) if s != 0]
+        self._pyr_n = len(lv)
+        self._pyr_outs = (C.c_void_p * max(len(lv), 1))(*[self.pyr[i].data_ptr() for i in lv])
+        self._pyr_hs = (C.c_int32 * max(len(lv), 1))(*[self.hw[i][0] for i in lv])
+        self._pyr_ws = (C.c_int32 * max(len(lv), 1))(*[self.hw[i][1] for i in lv])
         self._pa = FsPhotoArgs()
         self._sa = FsSmoothArgs()
         self.seed_buf = torch.zeros(1, dtype=torch.int32, device=device)   # device-resident tie-break seed
@@ -514,11 +520,10 @@ class PhotometricLoss:
         else:
             self.acc.zero_()
         self._clean_acc = False
-        for i, s in enumerate(self.scales):
-            if s != 0:
-                check(lib.fs_color_pyramid(img0.data_ptr(), self.pyr[i].data_ptr(), self.B, self.H, self.W,
-                                           self.hw[i][0], self.hw[i][1], st), "color_pyramid")
-        check(lib.fs_photo_identity(pa, st), "photo_identity")
+        if self._pyr_n:
+            check(lib.fs_color_pyramid_multi(img0.data_ptr(), self._pyr_outs, self._pyr_hs, self._pyr_ws, self._pyr_n,
+                                             self.B, self.H, self.W, st), "color_pyramid_multi")
+        check(lib.fs_photo_identity_rows(pa, st), "photo_identity_rows")
 
     def _fill(self, img0, srcs, patched_mask, depths, disps, noise_seed, gout):
         pa, sa = self._pa, self._sa

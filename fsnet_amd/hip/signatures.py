@@ -91,6 +91,9 @@ SIGNATURES = {
     "fs_mei_stage_mask": (C.c_int, [P, P, P, I, I, I, P]),
     "fs_mei_points": (C.c_int, [P, P, P, I, I, I, P]),
     "fs_photo_identity": (C.c_int, [P, P]),
+    # added under ABI 15: the row-walking identity kernel and its strip height
+    "fs_photo_identity_rows": (C.c_int, [P, P]),
+    "fs_photo_identity_strip_rows": (C.c_int, []),
     "fs_photo_fused_fwd": (C.c_int, [P, P]),
     "fs_photo_fused_bwd": (C.c_int, [P, P]),
     "fs_photo_fused_bwd_tiles": (C.c_int64, [I, I]),
@@ -98,6 +101,8 @@ SIGNATURES = {
     "fs_augment_frames": (C.c_int, [P, P]),
     "fs_resize_frames": (C.c_int, [P, P]),
     "fs_color_pyramid": (C.c_int, [P, P, I, I, I, I, I, P]),
+    # added under ABI 15: (img, outs[n], hs[n], ws[n], n, B, H, W, stream) — all levels from one read of the image
+    "fs_color_pyramid_multi": (C.c_int, [P, P, P, P, I, I, I, I, P]),
     "fs_smooth_mean": (C.c_int, [P, P]),
     "fs_smooth_fwd": (C.c_int, [P, P]),
     "fs_smooth_bwd": (C.c_int, [P, P]),

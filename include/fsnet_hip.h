@@ -697,6 +697,7 @@ int fs_pose_tail_bwd(const float* x, const float* dT, void* dx, int B, int hw, i
  * Images are planar NCHW fp32; all S scales are processed per launch.
  *   fs_photo_setup     K, K^-1 (f64), P_f = (K T_f)[:3] per batch element -> geo [B][48]
  *   fs_photo_identity  identity reprojection losses ident[B][2][H][W]; mask_sum[b] += sum(patched_mask[b])
+ *                      (fs_photo_identity_rows: the form the training step calls)
  *   fs_photo_fused_fwd warp (bilinear/border + nearest/zeros overlap sample) and loss of all scales and both frames:
  *                      sel[S][B][H][W] (argmin: 0,1 identity; 2,3 reprojection), loss_sums[s][b] += masked sum;
  *                      optionally pred[S][2][B][3][H][W], ov[S][2][B][H][W]
@@ -746,6 +747,16 @@ int fs_photo_setup(const float* P2, const float* T0, const float* T1, float* geo
                    int fisheye, void* stream);   /* seed_counter (or NULL): device int bumped by one — the noise seed of
                                                     this step */
 int fs_photo_identity(const FsPhotoArgs* args, void* stream);
+/* fs_photo_identity_rows (added under ABI 15): the same two planes and mask sum from one read of the nine input planes —
+ * a wave walks a strip of 62 columns x fs_photo_identity_strip_rows() rows top to bottom (horizontal window sums by
+ * DPP, the last two rows' sums in registers, no LDS).  Values agree with fs_photo_identity's to rounding, not bit for
+ * bit, for two reasons: the nine taps of a window are added in another order (fs_photo_identity keeps the
+ * reference's), and the SSIM quotient n / d is a reciprocal with one Newton step and the mean over the channels a
+ * multiplication by 1/3, each within 1 ulp of the division.  A source frame equal to the target still gives exactly
+ * 0, and the result is the same from run to run.  Any B >= 1, H >= 2,
+ * W >= 2 with 3 * H * W < 2^30. */
+int fs_photo_identity_rows(const FsPhotoArgs* args, void* stream);
+int fs_photo_identity_strip_rows(void);
 /* (ABI <= 9 also had the staged form fs_photo_warp / fs_photo_loss_fwd / fs_photo_loss_bwd / fs_photo_bwd_tiles.)
  * fs_photo_fused_fwd: ONE launch for all scales and both frames, the warped images stay in registers (pred / ov may be
  * NULL; when given they are written for logging and for outputs[("original_image", f, s)] of _generate_images_pred
@@ -789,6 +800,11 @@ typedef struct FsSmoothArgs {
   int32_t B, S;
 } FsSmoothArgs;
 int fs_color_pyramid(const float* img, float* out, int B, int H, int W, int h, int w, void* stream);
+/* n (<= 4) levels of one image, outs[i] = [B][3][hs[i]][ws[i]] (outs / hs / ws are host arrays).  Exactly the ratios
+ * 2, 4 and 8 of an image whose sides are multiples of 8 are written by ONE launch from one read of the image; anything
+ * else runs fs_color_pyramid's kernel per level.  Either way every output is bit-identical to fs_color_pyramid's. */
+int fs_color_pyramid_multi(const float* img, float* const* outs, const int32_t* hs, const int32_t* ws, int n, int B,
+                           int H, int W, void* stream);
 int fs_smooth_mean(const FsSmoothArgs* args, void* stream);
 int fs_smooth_fwd(const FsSmoothArgs* args, void* stream);
 int fs_smooth_bwd(const FsSmoothArgs* args, void* stream);
