@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void photo_fused_fwd_kernel(const FsPhotoArgs 
   const bool col_out = lane >= 1 && lane <= FW && x < W;
   const int ys = sy * FRH;
   const int seed = p.noise_seed_ptr ? (*p.noise_seed_ptr & 0x3fffffff) : p.noise_seed;
-  const float k9 = 1.f / 9.f, k3 = 1.f / 3.f;
+  const float k9 = 1.f / 9.f, k81 = 1.f / 81.f, k3 = 1.f / 3.f;
   const float wm1 = (float)(W - 1), hm1 = (float)(H - 1);
   const float iwm1 = 1.f / wm1, ihm1 = 1.f / hm1;
   const bool have_mask = p.warp_mask || p.patched_mask;
@@ -246,11 +246,13 @@ __global__ __launch_bounds__(256) void photo_fused_fwd_kernel(const FsPhotoArgs 
     for (int c = 0; c < 3; ++c) {
       const float sy_ = (r2.t[c] + r1.t[c]) + r0.t[c], syy = (r2.tt[c] + r1.tt[c]) + r0.tt[c];
       const float muy = sy_ * k9;
-      const float sgy = syy * k9 - muy * muy;
+      // (co)variances as (9 sum(ab) - sum(a) sum(b)) / 81: with the rounded 1 / 9 in both terms of E[ab] - E[a] E[b] its
+      // rounding error, times mu^2, survives the cancellation and shifts every SSIM term the same way (+1.5e-7 on average)
+      const float sgy = (9.f * syy - sy_ * sy_) * k81;
       const f2 sxs = (r2.x[c] + r1.x[c]) + r0.x[c], sxx = (r2.xx[c] + r1.xx[c]) + r0.xx[c],
                sxy = (r2.xt[c] + r1.xt[c]) + r0.xt[c];
       const f2 mux = sxs * k9;
-      const f2 sgx = sxx * k9 - mux * mux, sgxy = sxy * k9 - mux * muy;
+      const f2 sgx = (9.f * sxx - sxs * sxs) * k81, sgxy = (9.f * sxy - sxs * sy_) * k81;
       const f2 n = (2.f * mux * muy + C1) * (2.f * sgxy + C2);
       const f2 d = (mux * mux + muy * muy + C1) * (sgx + sgy + C2);
       const f2 q = FISH ? n / d : n * f2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
@@ -358,7 +360,7 @@ __global__ __launch_bounds__(256) void photo_fused_bwd_kernel(const FsPhotoArgs 
   const bool last_x = x0s + BW >= W, last_y = ys + BRH >= H;
   const bool col_own = (lane >= 2 && lane < 2 + BW && x < W) || (x == -1) || (x == W && last_x);   // x == -1 only when sx == 0
   const int q_lo = ys == 0 ? -1 : ys, q_hi = last_y ? H : ys + BRH - 1;
-  const float k9 = 1.f / 9.f;
+  const float k9 = 1.f / 9.f, k81 = 1.f / 81.f;
   const float wm1 = (float)(W - 1), hm1 = (float)(H - 1);
   const float iwm1 = 1.f / wm1, ihm1 = 1.f / hm1;
   double msum = 0.0;
@@ -417,12 +419,14 @@ __global__ __launch_bounds__(256) void photo_fused_bwd_kernel(const FsPhotoArgs 
       const float fyu = sh * (float)yr;
       const int dy0 = h > 1 ? min((int)fyu, h - 2) : 0;
       const float dly = h > 1 ? fyu - (float)dy0 : 0.f;
+      // (a one-row map has dly = 0 and reads its row twice; a one-column map has dlx = 0: the same blend as the forward)
+      const int dy1 = dy0 + (h > 1 ? 1 : 0);
       float d00, d01, d10, d11;
-      if (w > 1 && h > 1) {
-        const F2u a = ldg2(dmap, (unsigned)(dy0 * w + dx0) * 4u), c2_ = ldg2(dmap, (unsigned)((dy0 + 1) * w + dx0) * 4u);
+      if (w > 1) {
+        const F2u a = ldg2(dmap, (unsigned)(dy0 * w + dx0) * 4u), c2_ = ldg2(dmap, (unsigned)(dy1 * w + dx0) * 4u);
         d00 = a.a; d01 = a.b; d10 = c2_.a; d11 = c2_.b;
       } else {
-        d00 = d01 = d10 = d11 = ldg(dmap, (unsigned)(dy0 * w + dx0) * 4u);
+        d00 = d01 = ldg(dmap, (unsigned)(dy0 * w) * 4u); d10 = d11 = ldg(dmap, (unsigned)(dy1 * w) * 4u);
       }
       r0.D = (1.f - dly) * ((1.f - dlx) * d00 + dlx * d01) + dly * ((1.f - dlx) * d10 + dlx * d11);
     }
@@ -477,7 +481,8 @@ __global__ __launch_bounds__(256) void photo_fused_bwd_kernel(const FsPhotoArgs 
       const C3 sxx = (r2.xx + r1.xx) + r0.xx, syy = (r2.tt + r1.tt) + r0.tt;
       const C3 sxy = (r2.xt + r1.xt) + r0.xt;
       const C3 mux = sxs * k9, muy = sys_ * k9;
-      const C3 sgx = sxx * k9 - mux * mux, sgy = syy * k9 - muy * muy, sgxy = sxy * k9 - mux * muy;
+      const C3 sgx = (9.f * sxx - sxs * sxs) * k81, sgy = (9.f * syy - sys_ * sys_) * k81,      // (as the forward)
+               sgxy = (9.f * sxy - sxs * sys_) * k81;
       const C3 n1 = 2.f * mux * muy + C1, n2 = 2.f * sgxy + C2;
       const C3 d1 = mux * mux + muy * muy + C1, d2 = sgx + sgy + C2;
       const C3 n = n1 * n2, d = d1 * d2;

@@ -155,7 +155,13 @@ __global__ __launch_bounds__(256) void photo_ident_kernel(const FsPhotoArgs p) {
 // lane / halo row loads the reflected pixel.  The nine taps are added as (row sums of three) of three instead of one
 // after the other, so a value may differ from reproj_at()'s in the last bits; after the sums it is the same unfused
 // arithmetic except for the quotient (div_nr) and the two means over the channels (x 1/3), with sigma_x, sigma_t and
-// sigma_xt in one expression shape: a frame equal to the target still gives exactly 0.  The next row's loads are
+// sigma_xt in one expression shape: a frame equal to the target still gives exactly 0.
+// The window sums are taken of (value - 0.5) and the (co)variances formed as (9 sum(ab) - sum(a) sum(b)) / 81.  Variances do
+// not move with a shift and images live in [0, 1], so the two terms that cancel are ~ 10 x smaller than with the raw
+// values and the result's fp32 noise with them (largest error against f64 over the shapes of the test: 2.5e-7, the tile
+// kernel's 1.6e-6).  And no rounded constant stands inside the cancellation: reproj_at()'s sum k - mu mu with k = fl(1 / 9)
+// keeps that constant's rounding error times mu^2, which raises every SSIM term by 1.5e-7 on average: a tenth of the
+// noise, but one-sided, so it shows in the loss sums (tests/test_photo_fused_seams_gpu.py).  The next row's loads are
 // issued into the ring slot whose raw values are no longer needed before the current row is worked on.
 // Strip height: a strip re-reads (and re-sums) 2 halo rows, so ID_RS = 16 costs 12.5 % more rows than the image has
 // (8: 25 %, 32: 6 %).  Measured alone at 192x640 / batch 12 and 384x384 / batch 16, inputs from HBM: 8 rows 43.8 /
@@ -219,25 +225,27 @@ __global__ __launch_bounds__(256) void photo_ident_rows_kernel(const FsPhotoArgs
     load(r2, min(it + 1, nsteps - 1));               // next row (this step reads r2's sums only); last step: a re-load, unused
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      r0.t[c] = hsum3(r0.rt[c]);
-      r0.tt[c] = hsum3(r0.rt[c] * r0.rt[c]);
-      r0.x[c] = hsum3(r0.rx[c]);
-      r0.xx[c] = hsum3(r0.rx[c] * r0.rx[c]);
-      r0.xt[c] = hsum3(r0.rx[c] * r0.rt[c]);
+      const float tc = r0.rt[c] - 0.5f;              // (exact from 0.25 up, half an ulp of 0.5 below)
+      const f2 xc = r0.rx[c] - 0.5f;
+      r0.t[c] = hsum3(tc);
+      r0.tt[c] = hsum3(tc * tc);
+      r0.x[c] = hsum3(xc);
+      r0.xx[c] = hsum3(xc * xc);
+      r0.xt[c] = hsum3(xc * tc);
     }
     if (it < 2) return;
     const int yc = ys + it - 2;                      // < H by nsteps
-    const float k = 1.f / 9.f;
+    const float k = 1.f / 9.f, k81 = 1.f / 81.f;
     f2 ssim_sum = splat(0.f), l1 = splat(0.f);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float sy_ = (r2.t[c] + r1.t[c]) + r0.t[c], syy = (r2.tt[c] + r1.tt[c]) + r0.tt[c];
       const f2 sxs = (r2.x[c] + r1.x[c]) + r0.x[c], sxx = (r2.xx[c] + r1.xx[c]) + r0.xx[c],
                sxy = (r2.xt[c] + r1.xt[c]) + r0.xt[c];
-      const float muy = sy_ * k;
-      const f2 mux = sxs * k;
-      const float sgy = syy * k - muy * muy;
-      const f2 sgx = sxx * k - mux * mux, sgxy = sxy * k - mux * muy;
+      const float muy = sy_ * k + 0.5f;
+      const f2 mux = sxs * k + 0.5f;
+      const float sgy = (9.f * syy - sy_ * sy_) * k81;
+      const f2 sgx = (9.f * sxx - sxs * sxs) * k81, sgxy = (9.f * sxy - sxs * sy_) * k81;
       const f2 n = (2.f * mux * muy + C1) * (2.f * sgxy + C2);
       const f2 d = (mux * mux + muy * muy + C1) * (sgx + sgy + C2);
       const f2 sv = (1.f - f2{div_nr(n.x, d.x), div_nr(n.y, d.y)}) * 0.5f;
