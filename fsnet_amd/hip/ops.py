@@ -833,18 +833,17 @@ class _LidarDepth:
     `offsets` [G + 1] into it, and the `depth` maps.  Buffers are kept between calls of the same (G, H, W) so that a
     call can be captured into a graph and replayed: stage() copies the inputs into them, run() issues the kernels only."""
 
-    def __init__(self, name, workspace_bytes, G, H, W, device):
-        self.G, self.H, self.W, self.device = G, H, W, torch.device(device)
-        ws = int(workspace_bytes(G, H, W))
+    def __init__(self, name, workspace_bytes, shape, dtype, device):
+        """workspace_bytes: what the entry point's *_workspace_bytes gives for this shape; shape, dtype: of `depth`,
+        (G, ..., H, W)"""
+        self.G, self.H, self.W, self.device = shape[0], shape[-2], shape[-1], torch.device(device)
+        ws = int(workspace_bytes)
         if ws < 0:
-            raise ValueError("%s: bad shape G=%d H=%d W=%d" % (name, G, H, W))
+            raise ValueError("%s: bad shape G=%d H=%d W=%d" % (name, self.G, self.H, self.W))
         self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
-        self.offsets = torch.zeros(G + 1, dtype=torch.int64, device=self.device)
-        self.depth = self._alloc_depth()
+        self.offsets = torch.zeros(self.G + 1, dtype=torch.int64, device=self.device)
+        self.depth = torch.empty(*shape, dtype=dtype, device=self.device)
         self.points = torch.empty(0, 4, dtype=torch.float32, device=self.device)
-
-    def _alloc_depth(self):
-        return torch.empty(self.G, self.H, self.W, dtype=torch.float32, device=self.device)
 
     def _stage_scans(self, scans):
         """scans: G float32 [Ni, 4] arrays / tensors"""
@@ -872,7 +871,8 @@ class LidarMeiDepth(_LidarDepth):
     kitti360_fisheye_eval.py:97-145)."""
 
     def __init__(self, G, H, W, device):
-        super().__init__("lidar_mei_depth", lib.fs_lidar_mei_depth_workspace_bytes, G, H, W, device)
+        super().__init__("lidar_mei_depth", lib.fs_lidar_mei_depth_workspace_bytes(G, H, W), (G, H, W), torch.float32,
+                         device)
         self.T = torch.zeros(G, 16, dtype=torch.float64, device=self.device)
         self.mei = torch.zeros(G, 7, dtype=torch.float64, device=self.device)
         self.close_mask = torch.empty(G, H, W, dtype=torch.uint8, device=self.device)
@@ -903,7 +903,8 @@ class LidarPinholeDepth(_LidarDepth):
     (fs_lidar_pinhole_depth; monodepth_utils.py:422-458)."""
 
     def __init__(self, G, H, W, device):
-        super().__init__("lidar_pinhole_depth", lib.fs_lidar_pinhole_depth_workspace_bytes, G, H, W, device)
+        super().__init__("lidar_pinhole_depth", lib.fs_lidar_pinhole_depth_workspace_bytes(G, H, W), (G, H, W),
+                         torch.float32, device)
         self.P = torch.zeros(G, 12, dtype=torch.float64, device=self.device)
 
     def stage(self, scans, P):
@@ -933,12 +934,9 @@ class LidarNuscDepth(_LidarDepth):
 
     def __init__(self, G, C, H, W, device):
         self.C = int(C)
-        super().__init__("lidar_nusc_depth", lambda g, h, w: lib.fs_lidar_nusc_depth_workspace_bytes(g, self.C, h, w),
-                         G, H, W, device)
+        super().__init__("lidar_nusc_depth", lib.fs_lidar_nusc_depth_workspace_bytes(G, self.C, H, W),
+                         (G, self.C, H, W), torch.int16, device)
         self.M = torch.zeros(G, self.C, 12, dtype=torch.float64, device=self.device)
-
-    def _alloc_depth(self):
-        return torch.empty(self.G, self.C, self.H, self.W, dtype=torch.int16, device=self.device)
 
     def stage(self, scans, M):
         """scans: G float32 [Ni, 4] arrays / tensors (ego-frame x, y, z, one unused lane); M: f64 [G, C, 3, 4], rows

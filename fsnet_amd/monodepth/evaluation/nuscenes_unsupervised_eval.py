@@ -5,9 +5,11 @@ reference calls — LidarPointCloud.from_file / remove_close / transform, transf
 are restated here in numpy.
 
 `_precompute` exports one LiDAR sweep per sample through its six cameras as 16-bit PNGs, <gt_saved_dir>/<CAM>/<name>.png.
+It lists every sample's six jobs first (file name, size, matrix: metadata only), then walks them in groups of up to
+`group_size` consecutive samples whose cameras' sizes agree (size_runs) and reads a group's sweeps inside the group.
 With a GPU the projection, the last-writer scatter, the duplicate pass and the uint16 cast are fs_lidar_nusc_depth_u16,
-`group_size` samples x six cameras per call; without one it is nusc_depth_u16 below, the kernel's operation order in
-numpy.  Both write the same files.  generate_depth_map keeps the reference's signature and f64 result.
+one call per group; without one it is nusc_depth_u16 below, the kernel's operation order in numpy.  Both write the same
+files.  generate_depth_map keeps the reference's signature and f64 result.
 
 Scoring (`_single_loss`, `single_call`, `device_errors`, `__call__`) is fs_depth_eval_masked: 1e-3 < gt < 80, the median
 ratio, the clamp and the seven errors of the KITTI evaluator, inside the reference's crop — which here starts at
@@ -25,7 +27,7 @@ import torch
 
 from fsnet_amd.hip import ops
 from fsnet_amd.monodepth.data.datasets.utils import read_png16, write_png16
-from fsnet_amd.monodepth.evaluation.kitti_unsupervised_eval import KittiEigenEvaluator
+from fsnet_amd.monodepth.evaluation.kitti_unsupervised_eval import KittiEigenEvaluator, lidar_op, size_runs
 from fsnet_amd.monodepth.networks.utils.monodepth_utils import scatter_depth
 from fsnet_amd.vision_base.data.datasets.nuscenes_utils import NuScenes
 
@@ -213,27 +215,18 @@ class NuscenesEvaluator(KittiEigenEvaluator):
         nusc = NuScenes(version=nuscenes_version, dataroot=data_path, verbose=True)
         for cam in CAMS:
             os.makedirs(os.path.join(gt_saved_dir, cam), exist_ok=True)
-        pending = []                       # (sweep float32 [n, 4], jobs) of up to group_size samples
-
-        def flush():
-            if not pending:
-                return
-            for (_, jobs), planes in zip(pending, self._project([p[0] for p in pending], [p[1] for p in pending])):
-                for (depth_name, _, _), plane in zip(jobs, planes):
-                    write_png16(depth_name, plane)
-            del pending[:]
-
+        samples = []                       # (sample record, jobs): metadata only; a group's sweeps are read below
         for token in self.token_list:
             rec = nusc.get('sample', token)
-            lidar_data, lidar_mask = get_lidar(nusc, rec)
-            lidar = np.ascontiguousarray(lidar_data[lidar_mask == 1, :4])
-            jobs = self._export_jobs(nusc, rec, gt_saved_dir)
-            if pending and [j[1] for j in jobs] != [j[1] for j in pending[0][1]]:
-                flush()
-            pending.append((lidar, jobs))
-            if len(pending) == self.group_size:
-                flush()
-        flush()
+            samples.append((rec, self._export_jobs(nusc, rec, gt_saved_dir)))
+        for group in size_runs(samples, lambda s: [j[1] for j in s[1]], self.group_size):
+            sweeps = []                    # float32 [n, 4] each
+            for rec, _ in group:
+                lidar_data, lidar_mask = get_lidar(nusc, rec)
+                sweeps.append(np.ascontiguousarray(lidar_data[lidar_mask == 1, :4]))
+            for (_, jobs), planes in zip(group, self._project(sweeps, [s[1] for s in group])):
+                for (depth_name, _, _), plane in zip(jobs, planes):
+                    write_png16(depth_name, plane)
 
     def _project(self, sweeps, jobs):
         """-> per sample, per camera, the uint16 plane [H, W].  On the device when export_on_device and the cameras
@@ -245,10 +238,8 @@ class NuscenesEvaluator(KittiEigenEvaluator):
         if not self.export_on_device or len(sizes) != 1:
             return [[nusc_depth_u16(s, j[2], j[1]) for j in sample] for s, sample in zip(sweeps, jobs)]
         (H, W), = sizes
-        G = len(sweeps)
-        op = getattr(self, '_op', None)
-        if op is None or (op.G, op.C, op.H, op.W) != (G, len(CAMS), H, W):
-            op = self._op = ops.LidarNuscDepth(G, len(CAMS), H, W, self._device_for())
+        op = self._op = lidar_op(getattr(self, '_op', None), ops.LidarNuscDepth, (len(sweeps), len(CAMS), H, W),
+                                 self._device_for())
         op.stage(sweeps, np.stack([np.stack([j[2] for j in sample]) for sample in jobs]))
         return op.run().cpu().numpy()
 
@@ -303,16 +294,6 @@ class NuscenesEvaluator(KittiEigenEvaluator):
         as its mask, then the resize, median ratio, clamp and seven errors of fs_depth_eval)"""
         B, H, W = gt.shape
         return ops.depth_eval_masked(pred, gt, self._crop_mask(B, H, W, gt.device), lo=1e-3, hi=80.0, crop=False)
-
-    def _single_loss(self, depth_0, gt_depth):
-        """depth_0: predicted depth [h, w] (device tensor, or numpy as in the reference); gt_depth: [H, W]."""
-        dev = self._device_for(depth_0)
-        pred = torch.as_tensor(depth_0, dtype=torch.float32).to(dev)
-        gt = torch.as_tensor(gt_depth, dtype=torch.float32).to(dev)
-        out = self._depth_eval(pred[None], gt[None])[0].cpu().numpy()
-        if out[15] == 0:
-            raise ValueError
-        return dict(ratio=np.float32(out[0]), error=tuple(out[1:8]), abs_error=tuple(out[8:15]))
 
     def single_call(self, depth_0, filename):
         return self._single_loss(depth_0, self._gt(self._gt_path(filename), self._device_for(depth_0)))
