@@ -5,8 +5,7 @@
 // and their autograd backward.  Batch statistics arrive as per-channel f64 (sum, sumsq) produced by
 // the conv epilogue (conv_igemm.hip) — under data parallelism the host all-reduces that small
 // buffer between the conv and this kernel (SyncBatchNorm semantics, scripts/train.py:101).
-#include "common.h"
-#include "fsnet_hip_internal.h"
+#include "bn_coeffs.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -35,65 +34,70 @@ __device__ __forceinline__ void split_row(long m, int H, int W, long& n, int& h,
 
 constexpr int MAXC = 2048;
 
+template <typename A> __host__ __device__ inline int bn_groups(const A& a) { return a.groups > 1 ? a.groups : 1; }
+
+// Two problems per launch (fsnet_hip_internal.h, FsDual): the statistics groups of both stack along blockIdx.z.  -> the
+// block's argument set (a reference into the kernarg pair: a copy would land in scratch), its group count G and the
+// group z this block works on: the rows [z*M/G, (z+1)*M/G) and the z-th statistics / saved-state slice.  The backward
+// kernels decode with this; the two forward kernels spell the same four lines out, because there — kernels that hand
+// the argument set to no other function — the compiler answers a helper (or a lambda that captures `p`) by loading
+// both problems' fields and selecting: 400 more instructions and a lost wave per SIMD in bn_apply_kernel.
+template <typename A>
+__device__ __forceinline__ const A& bn_problem(const FsDual<A, FsNoGeom>& d, int& G, int& z) {
+  const int prob = (int)blockIdx.z >= d.nb0 ? 1 : 0;
+  const A& p = d.a[prob];
+  G = bn_groups(p);
+  z = (int)blockIdx.z - (prob ? d.nb0 : 0);
+  return p;
+}
+
+// an [N, H, W, C] tensor with the given element strides has no gaps: rows address it as m * C, no (n, h, w) needed
+__host__ __device__ inline bool dense(long sN, long sH, long sW, int H, int W, int C) {
+  return sW == C && sH == (long)W * C && sN == (long)H * W * C;
+}
+
+// A replicate-padded buffer [N, H+2, W+2, C] holds interior pixel (h, w) at (h+1, w+1) and, for an edge pixel, at the
+// border copies next to it: site(hp, wp) is called for each.  (H, W >= 2: decoder maps are never a single row/column)
+template <typename F>
+__device__ __forceinline__ void for_pad_sites(int h, int w, int H, int W, F site) {
+  int hs[2] = {h + 1, 0}, ws[2] = {w + 1, 0};
+  int nh = 1, nw = 1;
+  if (h == 0) { hs[1] = 0; nh = 2; } else if (h == H - 1) { hs[1] = H + 1; nh = 2; }
+  if (w == 0) { ws[1] = 0; nw = 2; } else if (w == W - 1) { ws[1] = W + 1; nw = 2; }
+  for (int a = 0; a < nh; ++a)
+    for (int b = 0; b < nw; ++b) site(hs[a], ws[b]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
-__device__ inline void bn_channel_coeffs(const double* stats, const float* rmean, const float* rvar, int C, int c,
-                                         double count, float eps, float gamma, float beta, float& mean,
-                                         float& invstd, float& var_b, float& scale, float& shift) {
-  double m, v;
-  if (stats) {
-    double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < FS_STAT_SLOTS; ++k) { s1 += stats[(long)k * 2 * C + c]; s2 += stats[(long)k * 2 * C + C + c]; }
-    m = s1 / count; v = s2 / count - m * m;
-  }
-  else { m = rmean[c]; v = rvar[c]; }  // eval mode: running statistics
-  if (v < 0) v = 0;
-  mean = (float)m;
-  var_b = (float)v;
-  invstd = (float)(1.0 / sqrt(v + (double)eps));
-  scale = gamma * invstd;
-  shift = beta - mean * scale;
-}
-
 // BatchNorm statistics -> per-channel coefficients, without touching the activation: the normalisation itself is
 // applied by the convolution that consumes the tensor (FsConvArgs.pro_mode = 1, FsWgradArgs.pro_a) — "BatchNorm
-// folded into the operand staging".  Same arithmetic and running-statistics update as bn_apply_kernel's preamble.
+// folded into the operand staging".  The preamble of bn_apply_kernel without the pass over the tensor.
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const FsBnApplyArgs p, float* __restrict__ scale,
                                                           float* __restrict__ shift) {
-  const int C = p.C;
-  const int G = p.groups > 1 ? p.groups : 1;
-  const int z = blockIdx.y;
+  const int C = p.C, G = bn_groups(p), z = blockIdx.y;
   const long gstat = (long)FS_STAT_SLOTS * 2 * C;
-  const double* stats_z = p.stats ? p.stats + z * gstat : nullptr;
   const bool train = p.stats != nullptr;
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c < C) {
-    float mean, invstd, varb, sc, sh;
-    bn_channel_coeffs(stats_z, p.running_mean, p.running_var, C, c, p.count, p.eps, p.gamma[c], p.beta[c], mean, invstd, varb, sc, sh);
-    p.save_mean[z * C + c] = mean; p.save_invstd[z * C + c] = invstd;
-    scale[z * C + c] = sc; shift[z * C + c] = sh;
-    if (z == 0 && train && p.running_mean) {
-      float rm = p.running_mean[c], rv = p.running_var[c];
-      for (int g = 0; g < G; ++g) {
-        float mg = mean, vg = varb, t0, t1, t2;
-        if (g > 0) bn_channel_coeffs(p.stats + g * gstat, nullptr, nullptr, C, c, p.count, p.eps, 1.f, 0.f, mg, t0, vg, t1, t2);
-        double unb = p.count > 1.0 ? (double)vg * p.count / (p.count - 1.0) : (double)vg;
-        rm = (1.f - p.momentum) * rm + p.momentum * mg;
-        rv = (1.f - p.momentum) * rv + p.momentum * (float)unb;
-      }
-      p.running_mean[c] = rm; p.running_var[c] = rv;
-    }
+    const BnCoeffs k = bn_channel_coeffs(train ? p.stats + z * gstat : nullptr, p.running_mean, p.running_var, C, c, p.count, p.eps,
+                                         p.gamma[c], p.beta[c]);
+    p.save_mean[z * C + c] = k.mean; p.save_invstd[z * C + c] = k.invstd;
+    scale[z * C + c] = k.scale; shift[z * C + c] = k.shift;
+    if (z == 0 && train && p.running_mean)
+      bn_running_update(k, p.stats, G, C, c, p.count, p.eps, p.momentum, p.running_mean, p.running_var);
   }
   if (z == 0 && blockIdx.x == 0 && threadIdx.x == 0 && train && p.num_batches_tracked) *p.num_batches_tracked += G;
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void bn_apply_kernel(const FsDual<FsBnApplyArgs, FsNoGeom> d, const int fast) {
-  // two problems per launch (fsnet_hip_internal.h, FsDual): the statistics groups of both stack along blockIdx.z
+__global__ __launch_bounds__(256) void bn_apply_kernel(const FsDual<FsBnApplyArgs, FsNoGeom> d) {
+  // (bn_problem's decode, spelled out: see there)
   const int prob = (int)blockIdx.z >= d.nb0 ? 1 : 0;
   const FsBnApplyArgs& p = d.a[prob];
+  const int G = p.groups > 1 ? p.groups : 1;
+  const int z = (int)blockIdx.z - (prob ? d.nb0 : 0);
   // per-channel coefficients in dynamic LDS (4*C floats): a fixed MAXC-sized array would cap the occupancy of
   // these bandwidth-bound kernels at 4-5 blocks per CU
   extern __shared__ float bn_smem[];
@@ -109,9 +113,6 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const FsDual<FsBnApplyArg
   float* s_scale2 = bn_smem + 2 * SC; float* s_shift2 = bn_smem + 3 * SC;
   const bool has2 = p.gamma2 != nullptr;
   const bool train = p.stats != nullptr;
-  // statistics groups: blockIdx.z owns the rows [z*Mg, (z+1)*Mg) and the z-th statistics / saved-state slice
-  const int G = p.groups > 1 ? p.groups : 1;
-  const int z = (int)blockIdx.z - (prob ? d.nb0 : 0);
   const int Mg = p.M / G;
   const long gstat = (long)FS_STAT_SLOTS * 2 * C;
   const double* stats_z = p.stats ? p.stats + z * gstat : nullptr;
@@ -134,37 +135,17 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const FsDual<FsBnApplyArg
   }
   for (int cl = threadIdx.x; cl < SC; cl += 256) {
     const int c = c0 + cl;
-    float mean, invstd, varb, sc, sh;
-    bn_channel_coeffs(stats_z, p.running_mean, p.running_var, C, c, p.count, p.eps, p.gamma[c], p.beta[c], mean, invstd, varb, sc, sh);
-    s_scale[cl] = sc; s_shift[cl] = sh;
-    if (first) { p.save_mean[z * C + c] = mean; p.save_invstd[z * C + c] = invstd; }
-    if (first && z == 0 && train && p.running_mean) {
-      // one momentum update per group, in group order (= the order the reference calls the module in)
-      float rm = p.running_mean[c], rv = p.running_var[c];
-      for (int g = 0; g < G; ++g) {
-        float mg = mean, vg = varb, t0, t1, t2;
-        if (g > 0) bn_channel_coeffs(p.stats + g * gstat, nullptr, nullptr, C, c, p.count, p.eps, 1.f, 0.f, mg, t0, vg, t1, t2);
-        double unb = p.count > 1.0 ? (double)vg * p.count / (p.count - 1.0) : (double)vg;
-        rm = (1.f - p.momentum) * rm + p.momentum * mg;
-        rv = (1.f - p.momentum) * rv + p.momentum * (float)unb;
-      }
-      p.running_mean[c] = rm; p.running_var[c] = rv;
-    }
+    const BnCoeffs k = bn_channel_coeffs(stats_z, p.running_mean, p.running_var, C, c, p.count, p.eps, p.gamma[c], p.beta[c]);
+    s_scale[cl] = k.scale; s_shift[cl] = k.shift;
+    if (first) { p.save_mean[z * C + c] = k.mean; p.save_invstd[z * C + c] = k.invstd; }
+    if (first && z == 0 && train && p.running_mean)
+      bn_running_update(k, p.stats, G, C, c, p.count, p.eps, p.momentum, p.running_mean, p.running_var);
     if (has2) {
-      bn_channel_coeffs(stats2_z, p.running_mean2, p.running_var2, C, c, p.count, p.eps, p.gamma2[c], p.beta2[c], mean, invstd, varb, sc, sh);
-      s_scale2[cl] = sc; s_shift2[cl] = sh;
-      if (first) { p.save_mean2[z * C + c] = mean; p.save_invstd2[z * C + c] = invstd; }
-      if (first && z == 0 && train && p.running_mean2) {
-        float rm = p.running_mean2[c], rv = p.running_var2[c];
-        for (int g = 0; g < G; ++g) {
-          float mg = mean, vg = varb, t0, t1, t2;
-          if (g > 0) bn_channel_coeffs(p.stats2 + g * gstat, nullptr, nullptr, C, c, p.count, p.eps, 1.f, 0.f, mg, t0, vg, t1, t2);
-          double unb = p.count > 1.0 ? (double)vg * p.count / (p.count - 1.0) : (double)vg;
-          rm = (1.f - p.momentum) * rm + p.momentum * mg;
-          rv = (1.f - p.momentum) * rv + p.momentum * (float)unb;
-        }
-        p.running_mean2[c] = rm; p.running_var2[c] = rv;
-      }
+      const BnCoeffs k2 = bn_channel_coeffs(stats2_z, p.running_mean2, p.running_var2, C, c, p.count, p.eps, p.gamma2[c], p.beta2[c]);
+      s_scale2[cl] = k2.scale; s_shift2[cl] = k2.shift;
+      if (first) { p.save_mean2[z * C + c] = k2.mean; p.save_invstd2[z * C + c] = k2.invstd; }
+      if (first && z == 0 && train && p.running_mean2)
+        bn_running_update(k2, p.stats2, G, C, c, p.count, p.eps, p.momentum, p.running_mean2, p.running_var2);
     }
   }
   if (first && z == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
@@ -174,11 +155,12 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const FsDual<FsBnApplyArg
   __syncthreads();
 
   T* __restrict__ y = reinterpret_cast<T*>(p.y);
-  const bool dense_y = !p.pad_out && p.yW == C && p.yH == (long)p.W * C && p.yN == (long)p.H * p.W * C;
+  const bool dense_y = !p.pad_out && dense(p.yN, p.yH, p.yW, p.H, p.W, C);
   const long stride = (long)gridDim.x * 256;
-  if (fast && dense_y && scg_sh >= 0) {
-    // dense output (every encoder layer): fixed channel group per thread, coefficients in registers, the raw operands of
-    // two later rows in flight (see bn_bwd_apply_kernel)
+  if (dense_y && scg_sh >= 0) {
+    // dense output with a power-of-two lane count (every encoder layer; the loop below serves strided and padded outputs
+    // and the other widths): fixed channel group per thread, coefficients in registers, the raw operands of two later
+    // rows in flight (see bn_bwd_apply_kernel)
     if (i0 >= total) return;
     const int cl = (int)(i0 & (SCG - 1)) * V;
     const long step = (stride >> scg_sh) * C;
@@ -262,14 +244,9 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const FsDual<FsBnApplyArg
       storev<T>(y + n * p.yN + (long)h * p.yH + (long)w * p.yW + c, v);
     } else {
       // output buffer is [N, H+2, W+2, C] with a replicated border (consumer uses replicate padding)
-      // (H, W >= 2: decoder maps are never a single row/column)
-      int hs[2] = {h + 1, 0}, ws[2] = {w + 1, 0};
-      int nh = 1, nw = 1;
-      if (h == 0) { hs[1] = 0; nh = 2; } else if (h == p.H - 1) { hs[1] = p.H + 1; nh = 2; }
-      if (w == 0) { ws[1] = 0; nw = 2; } else if (w == p.W - 1) { ws[1] = p.W + 1; nw = 2; }
-      for (int a = 0; a < nh; ++a)
-        for (int b = 0; b < nw; ++b)
-          storev<T>(y + n * p.yN + (long)hs[a] * p.yH + (long)ws[b] * p.yW + c, v);
+      const long yH = p.yH, yW = p.yW;       // (the lambda must not capture p: see bn_problem)
+      T* yn = y + n * p.yN + c;
+      for_pad_sites(h, w, p.H, p.W, [&](int hp, int wp) { storev<T>(yn + hp * yH + wp * yW, v); });
     }
   }
 }
@@ -286,30 +263,19 @@ template <typename T>
 __global__ __launch_bounds__(256) void bn_apply_pool_kernel(const FsDual<FsBnApplyArgs, FsNoGeom> d) {
   const int prob = (int)blockIdx.z >= d.nb0 ? 1 : 0;
   const FsBnApplyArgs& p = d.a[prob];
+  const int G = p.groups > 1 ? p.groups : 1;
+  const int z = (int)blockIdx.z - (prob ? d.nb0 : 0);
   extern __shared__ float bn_smem[];
   const int C = p.C;
   float* s_scale = bn_smem; float* s_shift = bn_smem + C;
-  const int G = p.groups > 1 ? p.groups : 1;
-  const int z = (int)blockIdx.z - (prob ? d.nb0 : 0);
-  const long gstat = (long)FS_STAT_SLOTS * 2 * C;
-  const double* stats_z = p.stats + z * gstat;
   const bool first = blockIdx.x == 0;
+  const double* stats_z = p.stats + z * ((long)FS_STAT_SLOTS * 2 * C);      // (train mode only: the host sees to it)
   for (int c = threadIdx.x; c < C; c += 256) {
-    float mean, invstd, varb, sc, sh;
-    bn_channel_coeffs(stats_z, p.running_mean, p.running_var, C, c, p.count, p.eps, p.gamma[c], p.beta[c], mean, invstd, varb, sc, sh);
-    s_scale[c] = sc; s_shift[c] = sh;
-    if (first) { p.save_mean[z * C + c] = mean; p.save_invstd[z * C + c] = invstd; }
-    if (first && z == 0 && p.running_mean) {
-      float rm = p.running_mean[c], rv = p.running_var[c];
-      for (int g = 0; g < G; ++g) {
-        float mg = mean, vg = varb, t0, t1, t2;
-        if (g > 0) bn_channel_coeffs(p.stats + g * gstat, nullptr, nullptr, C, c, p.count, p.eps, 1.f, 0.f, mg, t0, vg, t1, t2);
-        double unb = p.count > 1.0 ? (double)vg * p.count / (p.count - 1.0) : (double)vg;
-        rm = (1.f - p.momentum) * rm + p.momentum * mg;
-        rv = (1.f - p.momentum) * rv + p.momentum * (float)unb;
-      }
-      p.running_mean[c] = rm; p.running_var[c] = rv;
-    }
+    const BnCoeffs k = bn_channel_coeffs(stats_z, p.running_mean, p.running_var, C, c, p.count, p.eps, p.gamma[c], p.beta[c]);
+    s_scale[c] = k.scale; s_shift[c] = k.shift;
+    if (first) { p.save_mean[z * C + c] = k.mean; p.save_invstd[z * C + c] = k.invstd; }
+    if (first && z == 0 && p.running_mean)
+      bn_running_update(k, p.stats, G, C, c, p.count, p.eps, p.momentum, p.running_mean, p.running_var);
   }
   if (first && z == 0 && threadIdx.x == 0 && p.num_batches_tracked) *p.num_batches_tracked += G;
   __syncthreads();
@@ -385,25 +351,23 @@ __device__ inline void load_dout(const FsBnBwdArgs& p, const T* dout, long n, in
   }
 #pragma unroll
   for (int j = 0; j < V; ++j) g[j] = 0.f;
-  int hs[2] = {h + 1, 0}, ws[2] = {w + 1, 0};
-  int nh = 1, nw = 1;
-  if (h == 0) { hs[1] = 0; nh = 2; } else if (h == p.H - 1) { hs[1] = p.H + 1; nh = 2; }
-  if (w == 0) { ws[1] = 0; nw = 2; } else if (w == p.W - 1) { ws[1] = p.W + 1; nw = 2; }
-  for (int a = 0; a < nh; ++a)
-    for (int b = 0; b < nw; ++b) {
-      float t[V];
-      loadv<T>(dout + n * p.gN + (long)hs[a] * p.gH + (long)ws[b] * p.gW + c, t);
+  for_pad_sites(h, w, p.H, p.W, [&](int hp, int wp) {
+    float t[V];
+    loadv<T>(dout + n * p.gN + (long)hp * p.gH + (long)wp * p.gW + c, t);
 #pragma unroll
-      for (int j = 0; j < V; ++j) g[j] += t[j];
-    }
+    for (int j = 0; j < V; ++j) g[j] += t[j];
+  });
+}
+
+// what the backward reads besides x — the gradient and, for the ReLU mask, the activation — is dense
+__device__ __forceinline__ bool dense_grad(const FsBnBwdArgs& p) {
+  return !p.fold && dense(p.gN, p.gH, p.gW, p.H, p.W, p.C) && (!p.relu || dense(p.yN, p.yH, p.yW, p.H, p.W, p.C));
 }
 
 template <typename T>
 __device__ inline void masked_grad(const FsBnBwdArgs& p, const T* dout, const T* yv, long m, int c, float* g) {
   constexpr int V = VecN<T>::N;
-  const long hw = (long)p.H * p.W;
-  if (!p.fold && p.gW == p.C && p.gH == (long)p.W * p.C && p.gN == hw * p.C &&
-      (!p.relu || (p.yW == p.C && p.yH == (long)p.W * p.C && p.yN == hw * p.C))) {      // dense: no (n, h, w)
+  if (dense_grad(p)) {      // no (n, h, w)
     loadv<T>(dout + m * p.C + c, g);
     if (p.relu) {
       float yy[V];
@@ -484,6 +448,67 @@ __device__ inline void pool_mask(const FsBnBwdArgs& p, const T* yv, long m, int 
   }
 }
 
+// dx = gamma*invstd * (g - sum_g/count - xhat * sum_gx/count): k = gamma * invstd, a = sum_g / count, b = sum_gx / count
+__device__ __forceinline__ float bn_dx(float g, float x, float mean, float istd, float k, float a, float b) {
+  const float xh = (x - mean) * istd;
+  return k * (g - a - xh * b);
+}
+
+// Tail of the first pass: the block's partial sums s1 = sum(g), s2 = sum(g * xhat) of LANES channel lanes x 256 / LANES
+// pixel lanes fold through LDS, and one f64 atomic per channel and kind goes to the block's statistics slot.
+template <int V>
+__device__ __forceinline__ void reduce_tail(const FsBnBwdArgs& p, float (*red)[V][256], const float* s1, const float* s2, int z,
+                                            int LANES, int cgl, int pl, int c, bool act) {
+  const int C = p.C, PL = 256 / LANES;
+#pragma unroll
+  for (int j = 0; j < V; ++j) { red[0][j][threadIdx.x] = s1[j]; red[1][j][threadIdx.x] = s2[j]; }
+  __syncthreads();
+  // threads (pl < 2*V) of each channel group finish one (kind, j) pair each
+  if (act && pl < 2 * V && pl < PL) {
+    for (int kj = pl; kj < 2 * V; kj += PL) {
+      const int kind = kj / V, j = kj % V;
+      float acc = 0.f;
+      for (int k = 0; k < PL; ++k) acc += red[kind][j][k * LANES + cgl];
+      double* sl = p.sums + ((long)z * FS_STAT_SLOTS + blockIdx.x % FS_STAT_SLOTS) * 2 * C;
+      atomicAdd(sl + kind * C + c + j, (double)acc);
+    }
+  }
+}
+
+// Preamble of the second pass: the coefficient table tab[5 or 6][SC] of channels c0 .. c0 + SC - 1 of group z in LDS —
+// a = sum_g / count, b = sum_gx / count, k = gamma * invstd, mean, invstd and, where wanted (POOL mode's ReLU mask), the
+// forward's shift — and dgamma / dbeta, added by the first block of the group.  With sums_local (SyncBN) `sums` are the
+// exchanged ones: dx comes from those, the parameter gradients from the local shard's (the data-parallel all-reduce of
+// gradients averages them later).  sums / sums_local: group z's slices — the caller derives them where it derives its
+// other per-group scalars, before it requests its first operands (derived here, behind those loads, the element-wise
+// kernel parked 16 more scalars in vector lanes).
+__device__ __forceinline__ void bn_bwd_coeffs(const FsBnBwdArgs& p, const double* sums, const double* sums_local, int G, int z, int c0,
+                                              int SC, bool want_shift, float* tab) {
+  const int C = p.C;
+  for (int cl = threadIdx.x; cl < SC; cl += 256) {
+    const int c = c0 + cl;
+    double sg, sgx, lg = 0.0, lgx = 0.0;
+    bn_sum_slots(sums, C, c, sg, sgx);
+    if (sums_local) bn_sum_slots(sums_local, C, c, lg, lgx);
+    const float mean = p.save_mean[z * C + c], istd = p.save_invstd[z * C + c], k = p.gamma[c] * istd;
+    tab[3 * SC + cl] = mean; tab[4 * SC + cl] = istd;
+    tab[2 * SC + cl] = k;
+    if (want_shift) tab[5 * SC + cl] = (p.beta ? p.beta[c] : 0.f) - mean * k;
+    tab[cl] = (float)(sg / p.count);
+    tab[SC + cl] = (float)(sgx / p.count);
+    if (blockIdx.x == 0) {
+      if (G > 1) {       // the groups' blocks add concurrently
+        if (p.dgamma) atomicAdd(p.dgamma + c, (float)(sums_local ? lgx : sgx));
+        if (p.dbeta) atomicAdd(p.dbeta + c, (float)(sums_local ? lg : sg));
+      } else {
+        if (p.dgamma) p.dgamma[c] += (float)(sums_local ? lgx : sgx);
+        if (p.dbeta) p.dbeta[c] += (float)(sums_local ? lg : sg);
+      }
+    }
+  }
+  __syncthreads();
+}
+
 // ---------------------------------------------------------------------------------------------
 // POOL mode by 2 x 2 pixel quads.  The per-pixel gather above (pool_grad) decodes four windows per pixel — two integer
 // divisions, eight gather loads and 128 compare / select operations per 16-byte vector: the stem's two backward passes ran
@@ -534,16 +559,14 @@ __device__ __forceinline__ void pool_quad(const FsBnBwdArgs& p, long nn, int a, 
 // pass 1 of POOL mode: a thread owns one 16-byte channel lane of one quad per iteration
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_pool_kernel(const FsDual<FsBnBwdArgs, FsNoGeom> d) {
-  const int prob = (int)blockIdx.z >= d.nb0 ? 1 : 0;
-  const FsBnBwdArgs& p = d.a[prob];
+  int G, z;
+  const FsBnBwdArgs& p = bn_problem(d, G, z);
   constexpr int V = VecN<T>::N;
   __shared__ float red[2][V][256];
   const int C = p.C, CG = C / V, PL = 256 / CG;          // CG: a power of two <= 32 (host)
   const int cgl = threadIdx.x % CG, pl = threadIdx.x / CG, c = cgl * V;
   const T* __restrict__ yv = reinterpret_cast<const T*>(p.y);
   const T* __restrict__ xv = reinterpret_cast<const T*>(p.x);
-  const int G = p.groups > 1 ? p.groups : 1;
-  const int z = (int)blockIdx.z - (prob ? d.nb0 : 0);
   const int H = p.H, W = p.W, Ho = H >> 1, Wo = W >> 1;
   const unsigned Qg = (unsigned)(p.M / G) / 4;           // quads of a statistics group (whole images)
   float mean[V], istd[V], sc[V], sh[V], s1[V], s2[V];
@@ -568,58 +591,22 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_pool_kernel(const FsDual<Fs
       for (int j = 0; j < V; ++j) { s1[j] += g[k][j]; s2[j] += g[k][j] * (x[k][j] - mean[j]) * istd[j]; }
     }
   }
-#pragma unroll
-  for (int j = 0; j < V; ++j) { red[0][j][threadIdx.x] = s1[j]; red[1][j][threadIdx.x] = s2[j]; }
-  __syncthreads();
-  if (pl < 2 * V && pl < PL) {
-    for (int kj = pl; kj < 2 * V; kj += PL) {
-      const int kind = kj / V, j = kj % V;
-      float acc = 0.f;
-      for (int k = 0; k < PL; ++k) acc += red[kind][j][k * CG + cgl];
-      double* sl = p.sums + ((long)z * FS_STAT_SLOTS + blockIdx.x % FS_STAT_SLOTS) * 2 * C;
-      atomicAdd(sl + kind * C + c + j, (double)acc);
-    }
-  }
+  reduce_tail<V>(p, red, s1, s2, z, CG, cgl, pl, c, true);
 }
 
 // pass 2 of POOL mode
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply_pool_kernel(const FsDual<FsBnBwdArgs, FsNoGeom> d) {
   extern __shared__ float bn_smem[];
-  const int prob = (int)blockIdx.z >= d.nb0 ? 1 : 0;
-  const FsBnBwdArgs& p = d.a[prob];
+  int G, z;
+  const FsBnBwdArgs& p = bn_problem(d, G, z);
   constexpr int V = VecN<T>::N;
   const int C = p.C, CG = C / V, PL = 256 / CG;
   float* s_a = bn_smem; float* s_b = bn_smem + C; float* s_k = bn_smem + 2 * C;
   float* s_mean = bn_smem + 3 * C; float* s_istd = bn_smem + 4 * C; float* s_sh = bn_smem + 5 * C;
-  const int G = p.groups > 1 ? p.groups : 1;
-  const int z = (int)blockIdx.z - (prob ? d.nb0 : 0);
   const double* sums = p.sums + (long)z * FS_STAT_SLOTS * 2 * C;
   const double* sums_local = p.sums_local ? p.sums_local + (long)z * FS_STAT_SLOTS * 2 * C : nullptr;
-  for (int c = threadIdx.x; c < C; c += 256) {
-    double sg = 0.0, sgx = 0.0, lg = 0.0, lgx = 0.0;
-#pragma unroll
-    for (int k = 0; k < FS_STAT_SLOTS; ++k) {
-      sg += sums[(long)k * 2 * C + c]; sgx += sums[(long)k * 2 * C + C + c];
-      if (sums_local) { lg += sums_local[(long)k * 2 * C + c]; lgx += sums_local[(long)k * 2 * C + C + c]; }
-    }
-    const float istd = p.save_invstd[z * C + c];
-    s_mean[c] = p.save_mean[z * C + c]; s_istd[c] = istd;
-    s_k[c] = p.gamma[c] * istd;
-    s_sh[c] = (p.beta ? p.beta[c] : 0.f) - s_mean[c] * s_k[c];     // the forward's shift
-    s_a[c] = (float)(sg / p.count);
-    s_b[c] = (float)(sgx / p.count);
-    if (blockIdx.x == 0) {
-      if (G > 1) {
-        if (p.dgamma) atomicAdd(p.dgamma + c, (float)(sums_local ? lgx : sgx));
-        if (p.dbeta) atomicAdd(p.dbeta + c, (float)(sums_local ? lg : sg));
-      } else {
-        if (p.dgamma) p.dgamma[c] += (float)(sums_local ? lgx : sgx);
-        if (p.dbeta) p.dbeta[c] += (float)(sums_local ? lg : sg);
-      }
-    }
-  }
-  __syncthreads();
+  bn_bwd_coeffs(p, sums, sums_local, G, z, 0, C, true, bn_smem);
   const int cgl = threadIdx.x % CG, pl = threadIdx.x / CG, c = cgl * V;
   const T* __restrict__ yv = reinterpret_cast<const T*>(p.y);
   const T* __restrict__ xv = reinterpret_cast<const T*>(p.x);
@@ -639,10 +626,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pool_kernel(const FsDual<FsB
       pool_mask<T>(p, yv, m, c, x[k], s_k + c, s_sh + c, g[k]);
       float o[V];
 #pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const float xh = (x[k][j] - s_mean[c + j]) * s_istd[c + j];
-        o[j] = s_k[c + j] * (g[k][j] - s_a[c + j] - xh * s_b[c + j]);
-      }
+      for (int j = 0; j < V; ++j) o[j] = bn_dx(g[k][j], x[k][j], s_mean[c + j], s_istd[c + j], s_k[c + j], s_a[c + j], s_b[c + j]);
       storev<T>(dx + m * C + c, o);
     }
   }
@@ -651,9 +635,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pool_kernel(const FsDual<FsB
 // pass 1: per-channel sum(g), sum(g * xhat) with g = dout * (y > 0).  A block covers CGB channel groups
 // (16-byte lanes) x PL pixel lanes; two rows per iteration keep more loads in flight.
 template <typename T, int CGB, bool POOL = false>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const FsDual<FsBnBwdArgs, FsNoGeom> d, const int fast) {
-  const int prob = (int)blockIdx.z >= d.nb0 ? 1 : 0;
-  const FsBnBwdArgs& p = d.a[prob];
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const FsDual<FsBnBwdArgs, FsNoGeom> d) {
+  int G, z;
+  const FsBnBwdArgs& p = bn_problem(d, G, z);
   constexpr int V = VecN<T>::N;
   constexpr int PL = 256 / CGB;
   __shared__ float red[2][V][256];
@@ -665,8 +649,6 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const FsDual<FsBnBwd
   const T* __restrict__ dout = reinterpret_cast<const T*>(p.dout);
   const T* __restrict__ yv = reinterpret_cast<const T*>(p.y);
   const T* __restrict__ xv = reinterpret_cast<const T*>(p.x);
-  const int G = p.groups > 1 ? p.groups : 1;
-  const int z = (int)blockIdx.z - (prob ? d.nb0 : 0);
   const long Mg = p.M / G, m_end = (z + 1) * Mg;
   float mean[V], istd[V], s1[V], s2[V];
 #pragma unroll
@@ -708,10 +690,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const FsDual<FsBnBwd
   if (act) {
     const long stride = (long)gridDim.x * PL;
     long m = z * Mg + (long)blockIdx.x * PL + pl;
-    const long hw = (long)p.H * p.W;
-    if (fast && !p.fold && p.gW == C && p.gH == (long)p.W * C && p.gN == hw * C &&
-        (!p.relu || (p.yW == C && p.yH == (long)p.W * C && p.yN == hw * C))) {
-      // dense tensors: raw operands of two later rows in flight while the current row is summed (bn_bwd_apply_kernel)
+    if (dense_grad(p)) {
+      // dense tensors of 2-byte elements (fp32 ones go on to the loops below): raw operands of two later rows in flight while the current row is summed (bn_bwd_apply_kernel)
       const bool relu = p.relu != 0;
       long left = m < m_end ? (m_end - m + stride - 1) / stride : 0;
       long off = m * C + c;
@@ -764,27 +744,15 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const FsDual<FsBnBwd
       for (int j = 0; j < V; ++j) { s1[j] += g0[j]; s2[j] += g0[j] * (x0[j] - mean[j]) * istd[j]; }
     }
   }
-#pragma unroll
-  for (int j = 0; j < V; ++j) { red[0][j][threadIdx.x] = s1[j]; red[1][j][threadIdx.x] = s2[j]; }
-  __syncthreads();
-  // threads (pl < 2*V) of each channel group finish one (kind, j) pair each
-  if (act && pl < 2 * V && pl < PL) {
-    for (int kj = pl; kj < 2 * V; kj += PL) {
-      int kind = kj / V, j = kj % V;
-      float a = 0.f;
-      for (int k = 0; k < PL; ++k) a += red[kind][j][k * CGB + cgl];
-      double* sl = p.sums + ((long)z * FS_STAT_SLOTS + blockIdx.x % FS_STAT_SLOTS) * 2 * C;
-      atomicAdd(sl + kind * C + c + j, (double)a);
-    }
-  }
+  reduce_tail<V>(p, red, s1, s2, z, CGB, cgl, pl, c, act);
 }
 
 // pass 2: dx = gamma*invstd * (g - sum_g/count - xhat * sum_gx/count); optional g output; param grads
 template <typename T, bool POOL = false>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const FsDual<FsBnBwdArgs, FsNoGeom> d, const int fast) {
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const FsDual<FsBnBwdArgs, FsNoGeom> d) {
   extern __shared__ float bn_smem[];
-  const int prob = (int)blockIdx.z >= d.nb0 ? 1 : 0;
-  const FsBnBwdArgs& p = d.a[prob];
+  int G, z;
+  const FsBnBwdArgs& p = bn_problem(d, G, z);
   const int C = p.C;
   constexpr int V = VecN<T>::N;
   // channel slabs as in bn_apply_kernel (blockIdx.y: 32 channel groups of a row wider than that)
@@ -793,8 +761,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const FsDual<FsBnBwdA
   const int SC = SCG * V, c0 = (int)blockIdx.y * SC;
   float* s_a = bn_smem; float* s_b = bn_smem + SC; float* s_k = bn_smem + 2 * SC;
   float* s_mean = bn_smem + 3 * SC; float* s_istd = bn_smem + 4 * SC;
-  const int G = p.groups > 1 ? p.groups : 1;
-  const int z = (int)blockIdx.z - (prob ? d.nb0 : 0);
   const int Mg = p.M / G;
   const double* sums = p.sums + (long)z * FS_STAT_SLOTS * 2 * C;
   const double* sums_local = p.sums_local ? p.sums_local + (long)z * FS_STAT_SLOTS * 2 * C : nullptr;
@@ -813,32 +779,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const FsDual<FsBnBwdA
     else masked_grad<T>(p, dout, yv, m, c0 + cg * V, pg);
     loadv<T>(xv + m * C + c0 + cg * V, px);
   }
-  for (int cl = threadIdx.x; cl < SC; cl += 256) {
-    const int c = c0 + cl;
-    double sg = 0.0, sgx = 0.0, lg = 0.0, lgx = 0.0;
-#pragma unroll
-    for (int k = 0; k < FS_STAT_SLOTS; ++k) {
-      sg += sums[(long)k * 2 * C + c]; sgx += sums[(long)k * 2 * C + C + c];
-      if (sums_local) { lg += sums_local[(long)k * 2 * C + c]; lgx += sums_local[(long)k * 2 * C + C + c]; }
-    }
-    float istd = p.save_invstd[z * C + c];
-    s_mean[cl] = p.save_mean[z * C + c]; s_istd[cl] = istd;
-    s_k[cl] = p.gamma[c] * istd;
-    if constexpr (POOL) bn_smem[5 * SC + cl] = (p.beta ? p.beta[c] : 0.f) - s_mean[cl] * s_k[cl];     // the forward's shift
-    s_a[cl] = (float)(sg / p.count);
-    s_b[cl] = (float)(sgx / p.count);
-    if (blockIdx.x == 0) {
-      // dgamma / dbeta of the local shard (the data-parallel all-reduce of gradients averages them later)
-      if (G > 1) {       // the groups' blocks add concurrently
-        if (p.dgamma) atomicAdd(p.dgamma + c, (float)(sums_local ? lgx : sgx));
-        if (p.dbeta) atomicAdd(p.dbeta + c, (float)(sums_local ? lg : sg));
-      } else {
-        if (p.dgamma) p.dgamma[c] += (float)(sums_local ? lgx : sgx);
-        if (p.dbeta) p.dbeta[c] += (float)(sums_local ? lg : sg);
-      }
-    }
-  }
-  __syncthreads();
+  bn_bwd_coeffs(p, sums, sums_local, G, z, c0, SC, POOL, bn_smem);
   T* __restrict__ dx = reinterpret_cast<T*>(p.dx);
   T* __restrict__ gout = reinterpret_cast<T*>(p.g_out);
   const long stride = (long)gridDim.x * 256;
@@ -846,10 +787,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const FsDual<FsBnBwdA
     // Dense tensors (every ResNet layer): the thread's channel group is fixed, its rows advance by a constant — raw 16-byte
     // operands of TWO later rows stay in flight while the current one is processed (one row ahead left a wave with one
     // load per operand in flight: 2.5 TB/s on the 168 MB tensors of ResNet-50 layer 1 where a copy runs at 5.1)
-    const long hw = (long)p.H * p.W;
-    const bool plain = fast && !p.fold && scg_sh >= 0 && p.gW == C && p.gH == (long)p.W * C && p.gN == hw * C &&
-                       (!p.relu || (p.yW == C && p.yH == (long)p.W * C && p.yN == hw * C));
-    if (plain) {
+    if (scg_sh >= 0 && dense_grad(p)) {
       if (i0 >= total) return;
       const int cl = (int)(i0 & (SCG - 1)) * V;
       const long rows = stride >> scg_sh, step = rows * C;          // stride is a multiple of the (power-of-two) group count
@@ -875,10 +813,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const FsDual<FsBnBwdA
       for (int j = 0; j < V; ++j) { g[j] = pg[j]; xr[j] = px[j]; }
       for (;;) {
 #pragma unroll
-        for (int j = 0; j < V; ++j) {
-          float xh = (xr[j] - km[j]) * ki[j];
-          o[j] = kk[j] * (g[j] - ka[j] - xh * kb[j]);
-        }
+        for (int j = 0; j < V; ++j) o[j] = bn_dx(g[j], xr[j], km[j], ki[j], kk[j], ka[j], kb[j]);
         storev<T>(dx + off, o);
         if (gout) storev<T>(gout + off, g);
         if (--left == 0) break;
@@ -917,10 +852,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const FsDual<FsBnBwdA
     }
     if constexpr (POOL) pool_mask<T>(p, yv, m, c, xr, s_k + cl, bn_smem + 5 * SC + cl, g);
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-      float xh = (xr[j] - s_mean[cl + j]) * s_istd[cl + j];
-      o[j] = s_k[cl + j] * (g[j] - s_a[cl + j] - xh * s_b[cl + j]);
-    }
+    for (int j = 0; j < V; ++j) o[j] = bn_dx(g[j], xr[j], s_mean[cl + j], s_istd[cl + j], s_k[cl + j], s_a[cl + j], s_b[cl + j]);
     storev<T>(dx + m * C + c, o);
     if (gout) storev<T>(gout + m * C + c, g);
   }
@@ -953,7 +885,7 @@ extern "C" int fs_bn_finalize(const FsBnApplyArgs* a, float* scale, float* shift
   if (!a || !a->gamma || !a->beta || !a->save_mean || !a->save_invstd || !scale || !shift) return FS_EINVAL;
   if (!a->stats && (!a->running_mean || !a->running_var)) return FS_EINVAL;
   if (a->C <= 0 || a->C > MAXC || a->gamma2) return FS_EINVAL;
-  const int G = a->groups > 1 ? a->groups : 1;
+  const int G = bn_groups(*a);
   if (G > 1 && !a->stats) return FS_EINVAL;
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((a->C + 255) / 256, G), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      *a, scale, shift);
@@ -968,13 +900,13 @@ int bn_apply_check(const FsBnApplyArgs* a) {
     if (!a->pool_idx || !a->stats || a->res || a->gamma2 || a->pad_out || a->H <= 0 || a->W <= 0 || (a->H & 1) || (a->W & 1))
       return FS_EINVAL;
     if (a->M % (a->H * a->W) != 0 || (long)a->M * (a->C / 4) >= 0x7fffffffL) return FS_EINVAL;
-    if (a->y && !(a->yW == a->C && a->yH == (long)a->W * a->C && a->yN == (long)a->H * a->W * a->C)) return FS_EINVAL;
+    if (a->y && !dense(a->yN, a->yH, a->yW, a->H, a->W, a->C)) return FS_EINVAL;
   }
   if (!a->stats && (!a->running_mean || !a->running_var)) return FS_EINVAL;
   if (a->C % 8 != 0 || a->C > MAXC || a->M <= 0) return FS_EINVAL;
   if (a->gamma2 && (!a->res || !a->beta2 || !a->save_mean2 || !a->save_invstd2)) return FS_EINVAL;
   if (a->gamma2 && !a->stats2 && (!a->running_mean2 || !a->running_var2)) return FS_EINVAL;
-  const int G = a->groups > 1 ? a->groups : 1;
+  const int G = bn_groups(*a);
   if (a->M % G != 0 || (G > 1 && !a->stats)) return FS_EINVAL;
   return FS_OK;
 }
@@ -983,7 +915,7 @@ int bn_bwd_check(const FsBnBwdArgs* a, bool apply) {
   // common to both paths: channel tiling, the LDS table's extent, statistics groups, what the second pass writes
   if (apply && (!a->dx || !a->gamma)) return FS_EINVAL;
   if (a->C % 8 != 0 || a->C > MAXC || a->M <= 0) return FS_EINVAL;
-  const int G = a->groups > 1 ? a->groups : 1;
+  const int G = bn_groups(*a);
   if (a->M % G != 0) return FS_EINVAL;
   if (a->pool_dy) {
     if (!a->pool_idx || !a->gamma || a->fold || a->g_out || a->H <= 0 || a->W <= 0 || (a->H & 1) || (a->W & 1)) return FS_EINVAL;
@@ -991,158 +923,156 @@ int bn_bwd_check(const FsBnBwdArgs* a, bool apply) {
     const long hw = (long)a->H * a->W;
     // (a statistics group is a whole number of images: the quad mode walks 2x2 windows of one image)
     if (a->M % hw != 0 || (a->M / G) % hw != 0 || (long)a->M >= 0x7fffffffL) return FS_EINVAL;
-    if (a->dout && !(a->gW == a->C && a->gH == (long)a->W * a->C && a->gN == hw * a->C)) return FS_EINVAL;
-    if (a->y && !(a->yW == a->C && a->yH == (long)a->W * a->C && a->yN == hw * a->C)) return FS_EINVAL;
+    if (a->dout && !dense(a->gN, a->gH, a->gW, a->H, a->W, a->C)) return FS_EINVAL;
+    if (a->y && !dense(a->yN, a->yH, a->yW, a->H, a->W, a->C)) return FS_EINVAL;
     return FS_OK;
   }
   if (a->relu && !a->y) return FS_EINVAL;
   return FS_OK;
 }
+
+// One or two problems of an entry point fs_bn_*2(a, b, dtype, stream), as the launch sees them: the kernarg pair, the
+// group counts (G1 = 0 without b) and the extent that sizes the grid, which is that of the larger problem.
 template <typename A>
-FsDual<A, FsNoGeom> bn_dual(const A* a, const A* b) {
+struct BnPair {
   FsDual<A, FsNoGeom> d;
-  d.a[0] = *a; d.a[1] = b ? *b : *a;
-  d.g[0].unused = d.g[1].unused = 0;
-  d.nb0 = a->groups > 1 ? a->groups : 1;
-  d.nprob = b ? 2 : 1;
-  return d;
+  int G, G1;
+  template <typename F> long larger(F extent) const {      // extent(problem, its group count)
+    const long e = extent(d.a[0], G);
+    return d.nprob == 2 ? std::max(e, (long)extent(d.a[1], G1)) : e;
+  }
+};
+// Checks both problems and decides how they launch.  Two BatchNorms share a launch when they have the same width and
+// agree on POOL mode (`pool`: the member that switches it on) and, there, on the image size; a pair that does not is
+// issued as two calls of `single`.  -> true: launch pr; false: `status` is what the entry point returns (a refusal, or
+// the outcome of the two calls).  (`single` refuses an unsupported dtype itself, before it launches anything: so does the pair.)
+template <typename A, typename P, typename Check, typename Single>
+bool bn_pair(const A* a, const A* b, P A::*pool, Check check, Single single, BnPair<A>& pr, int& status) {
+  if ((status = check(a)) != FS_OK) return false;
+  if (b) {
+    if ((status = check(b)) != FS_OK) return false;
+    const bool pooled = a->*pool != nullptr;
+    if (b->C != a->C || pooled != (b->*pool != nullptr) || (pooled && (a->H != b->H || a->W != b->W))) {
+      status = single(a);
+      if (status == FS_OK) status = single(b);
+      return false;
+    }
+  }
+  pr.d.a[0] = *a; pr.d.a[1] = b ? *b : *a;
+  pr.d.g[0].unused = pr.d.g[1].unused = 0;
+  pr.d.nb0 = pr.G = bn_groups(*a);
+  pr.d.nprob = b ? 2 : 1;
+  pr.G1 = b ? bn_groups(*b) : 0;
+  return true;
+}
+
+// launch(Elem<T>{}) for the element type of `dtype`; any other dtype is refused before anything is launched
+template <typename T> struct Elem { using type = T; };
+template <typename F>
+int by_dtype(int dtype, F launch) {
+  if (dtype == FS_DTYPE_BF16) launch(Elem<bf16>{});
+  else if (dtype == FS_DTYPE_F32) launch(Elem<float>{});
+  else return FS_EINVAL;
+  return fs_launch_status();
+}
+int dtype_lanes(int dtype) { return dtype == FS_DTYPE_BF16 ? 8 : 4; }      // elements of a 16-byte lane
+
+// grid of the quad kernels: 256 / CG quads per block
+dim3 quad_grid(const long Qg, int CG, long cap, int groups) {
+  return dim3((unsigned)std::min<long>((Qg + 256 / CG - 1) / (256 / CG), cap), 1, groups);
+}
+template <typename A> long quads_per_group(const A& x, int G) { return (x.M / G) / 4; }
+template <typename A> long rows_per_group(const A& x, int G) { return x.M / G; }
+
+// first pass with CGB channel groups (16-byte lanes) per block
+template <int CGB>
+int launch_reduce(const BnPair<FsBnBwdArgs>& pr, int dtype, hipStream_t st, int CG, long rows_per_block, long max_blocks) {
+  const long Mg = pr.larger(rows_per_group<FsBnBwdArgs>);
+  const dim3 grid((unsigned)std::min<long>((Mg + rows_per_block - 1) / rows_per_block, max_blocks), (CG + CGB - 1) / CGB,
+                  pr.G + pr.G1);
+  return by_dtype(dtype, [&](auto e) {
+    using T = typename decltype(e)::type;
+    if (pr.d.a[0].pool_dy) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, CGB, true>), grid, dim3(256), 0, st, pr.d);
+    else hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, CGB>), grid, dim3(256), 0, st, pr.d);
+  });
 }
 }  // namespace
 
 // b != NULL: a second BatchNorm of the same width in the same launch (its statistics groups follow a's along blockIdx.z)
 extern "C" int fs_bn_apply2(const FsBnApplyArgs* a, const FsBnApplyArgs* b, int dtype, void* stream) {
-  int r = bn_apply_check(a);
-  if (r != FS_OK) return r;
-  if (b) {
-    r = bn_apply_check(b);
-    if (r != FS_OK) return r;
-    if (b->C != a->C || (a->pool_y != nullptr) != (b->pool_y != nullptr) || (a->pool_y && (a->H != b->H || a->W != b->W))) {
-      r = fs_bn_apply2(a, nullptr, dtype, stream);
-      return r != FS_OK ? r : fs_bn_apply2(b, nullptr, dtype, stream);
-    }
-  }
+  BnPair<FsBnApplyArgs> pr;
+  int r;
+  if (!bn_pair(a, b, &FsBnApplyArgs::pool_y, bn_apply_check,
+               [&](const FsBnApplyArgs* x) { return fs_bn_apply2(x, nullptr, dtype, stream); }, pr, r)) return r;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int vec = dtype == FS_DTYPE_BF16 ? 8 : 4;
-  const int G = a->groups > 1 ? a->groups : 1, G1 = b ? (b->groups > 1 ? b->groups : 1) : 0;
-  long items = (long)(a->M / G) * (a->C / vec);
-  if (b) items = std::max(items, (long)(b->M / G1) * (b->C / vec));
-  const FsDual<FsBnApplyArgs, FsNoGeom> d = bn_dual(a, b);
+  const int vec = dtype_lanes(dtype), nz = pr.G + pr.G1;
+  const long items = pr.larger([&](const FsBnApplyArgs& x, int G) { return (long)(x.M / G) * (x.C / vec); });
   if (a->pool_y) {
     // one thread per pooled pixel and 16-byte channel lane (nine window loads each): twice the element-wise passes' cap
-    dim3 pgrid(std::min(2 * grid_for(items / 4), (int)((items / 4 + 255) / 256)), 1, G + G1);
+    dim3 pgrid(std::min(2 * grid_for(items / 4), (int)((items / 4 + 255) / 256)), 1, nz);
     if (pgrid.x < 1) pgrid.x = 1;
     const unsigned plds = 2u * a->C * sizeof(float);
-    if (dtype == FS_DTYPE_BF16) hipLaunchKernelGGL(bn_apply_pool_kernel<bf16>, pgrid, dim3(256), plds, st, d);
-    else if (dtype == FS_DTYPE_F32) hipLaunchKernelGGL(bn_apply_pool_kernel<float>, pgrid, dim3(256), plds, st, d);
-    else return FS_EINVAL;
-    return fs_launch_status();
+    return by_dtype(dtype, [&](auto e) {
+      hipLaunchKernelGGL(bn_apply_pool_kernel<typename decltype(e)::type>, pgrid, dim3(256), plds, st, pr.d);
+    });
   }
   const int nslab = bn_slabs(a->C / vec);
-  dim3 grid(std::min(grid_for(items / nslab), std::max(32, grid_for(1L << 40) / nslab)), nslab, G + G1);   // (the cap holds per launch)
+  dim3 grid(std::min(grid_for(items / nslab), std::max(32, grid_for(1L << 40) / nslab)), nslab, nz);   // (the cap holds per launch)
   const unsigned lds = ((a->gamma2 || (b && b->gamma2)) ? 4u : 2u) * (a->C / nslab) * sizeof(float);
-  const int fast = 1;       // dense tensors take the kernels' fast path (the generic loop serves strided / padded ones)
-  if (dtype == FS_DTYPE_BF16) hipLaunchKernelGGL(bn_apply_kernel<bf16>, grid, dim3(256), lds, st, d, fast);
-  else if (dtype == FS_DTYPE_F32) hipLaunchKernelGGL(bn_apply_kernel<float>, grid, dim3(256), lds, st, d, fast);
-  else return FS_EINVAL;
-  return fs_launch_status();
+  return by_dtype(dtype, [&](auto e) {
+    hipLaunchKernelGGL(bn_apply_kernel<typename decltype(e)::type>, grid, dim3(256), lds, st, pr.d);
+  });
 }
 
 extern "C" int fs_bn_apply(const FsBnApplyArgs* a, int dtype, void* stream) { return fs_bn_apply2(a, nullptr, dtype, stream); }
 
 extern "C" int fs_bn_bwd_reduce2(const FsBnBwdArgs* a, const FsBnBwdArgs* b, int dtype, void* stream) {
-  int r = bn_bwd_check(a, false);
-  if (r != FS_OK) return r;
-  if (b) {
-    r = bn_bwd_check(b, false);
-    if (r != FS_OK) return r;
-    if (b->C != a->C || (a->pool_dy != nullptr) != (b->pool_dy != nullptr) || (a->pool_dy && (a->H != b->H || a->W != b->W))) {
-      r = fs_bn_bwd_reduce2(a, nullptr, dtype, stream);
-      return r != FS_OK ? r : fs_bn_bwd_reduce2(b, nullptr, dtype, stream);
-    }
-  }
+  BnPair<FsBnBwdArgs> pr;
+  int r;
+  if (!bn_pair(a, b, &FsBnBwdArgs::pool_dy, [](const FsBnBwdArgs* x) { return bn_bwd_check(x, false); },
+               [&](const FsBnBwdArgs* x) { return fs_bn_bwd_reduce2(x, nullptr, dtype, stream); }, pr, r)) return r;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int CG = a->C / (dtype == FS_DTYPE_BF16 ? 8 : 4);
-  const int G = a->groups > 1 ? a->groups : 1, G1 = b ? (b->groups > 1 ? b->groups : 1) : 0;
-  long Mg = a->M / G;
-  if (b) Mg = std::max<long>(Mg, b->M / G1);
-  const FsDual<FsBnBwdArgs, FsNoGeom> d = bn_dual(a, b);
+  const int CG = a->C / dtype_lanes(dtype), nz = pr.G + pr.G1;
   if (a->pool_dy && bn_pool_quads(CG)) {
-    long Qg = (a->M / G) / 4;
-    if (b) Qg = std::max<long>(Qg, (b->M / G1) / 4);
-    dim3 grid((unsigned)std::min<long>((Qg + 256 / CG - 1) / (256 / CG), 1024), 1, G + G1);
-    if (dtype == FS_DTYPE_BF16) hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel<bf16>, grid, dim3(256), 0, st, d);
-    else if (dtype == FS_DTYPE_F32) hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel<float>, grid, dim3(256), 0, st, d);
-    else return FS_EINVAL;
-    return fs_launch_status();
+    const dim3 grid = quad_grid(pr.larger(quads_per_group<FsBnBwdArgs>), CG, 1024, nz);
+    return by_dtype(dtype, [&](auto e) {
+      hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel<typename decltype(e)::type>, grid, dim3(256), 0, st, pr.d);
+    });
   }
   // channel groups (16-byte lanes) per block: 32 for wide layers (8 pixel lanes), 8, or — for the 16 / 32-channel
   // decoder layers, whose 2 / 4 lanes would leave three quarters of an 8-lane block idle — 4 and 2
-#define LAUNCH_REDUCE(CGB, ROWS_PER_BLOCK, MAXB)                                                               \
-  {                                                                                                             \
-    dim3 grid((unsigned)std::min<long>((Mg + (ROWS_PER_BLOCK) - 1) / (ROWS_PER_BLOCK), MAXB), (CG + CGB - 1) / CGB, G + G1); \
-    if (a->pool_dy) {                                                                                           \
-      if (dtype == FS_DTYPE_BF16) hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16, CGB, true>), grid, dim3(256), 0, st, d, 0);  \
-      else if (dtype == FS_DTYPE_F32) hipLaunchKernelGGL((bn_bwd_reduce_kernel<float, CGB, true>), grid, dim3(256), 0, st, d, 0); \
-      else return FS_EINVAL;                                                                                    \
-    } else                                                                                                      \
-    if (dtype == FS_DTYPE_BF16) hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16, CGB>), grid, dim3(256), 0, st, d, rfast);  \
-    else if (dtype == FS_DTYPE_F32) hipLaunchKernelGGL((bn_bwd_reduce_kernel<float, CGB>), grid, dim3(256), 0, st, d, rfast); \
-    else return FS_EINVAL;                                                                                      \
-  }
-  const int rfast = 1;
   // (wide rows: every block ends in 2 x 256 f64 atomics and a block-wide fold — hold the grid near 1024 blocks)
-  const long wide_cap = std::max<long>(32, std::min<long>(512, 1024 / ((long)((CG + 31) / 32) * (G + G1))));
-  if (CG >= 32) LAUNCH_REDUCE(32, 16, wide_cap)
-  else if (CG >= 8) LAUNCH_REDUCE(8, 64, 1024)
-  else if (CG >= 4) LAUNCH_REDUCE(4, 128, 1024)
-  else LAUNCH_REDUCE(2, 256, 1024)
-#undef LAUNCH_REDUCE
-  return fs_launch_status();
+  const long wide_cap = std::max<long>(32, std::min<long>(512, 1024 / ((long)((CG + 31) / 32) * nz)));
+  if (CG >= 32) return launch_reduce<32>(pr, dtype, st, CG, 16, wide_cap);
+  if (CG >= 8) return launch_reduce<8>(pr, dtype, st, CG, 64, 1024);
+  if (CG >= 4) return launch_reduce<4>(pr, dtype, st, CG, 128, 1024);
+  return launch_reduce<2>(pr, dtype, st, CG, 256, 1024);
 }
 
 extern "C" int fs_bn_bwd_reduce(const FsBnBwdArgs* a, int dtype, void* stream) { return fs_bn_bwd_reduce2(a, nullptr, dtype, stream); }
 
 extern "C" int fs_bn_bwd_apply2(const FsBnBwdArgs* a, const FsBnBwdArgs* b, int dtype, void* stream) {
-  int r = bn_bwd_check(a, true);
-  if (r != FS_OK) return r;
-  if (b) {
-    r = bn_bwd_check(b, true);
-    if (r != FS_OK) return r;
-    if (b->C != a->C || (a->pool_dy != nullptr) != (b->pool_dy != nullptr) || (a->pool_dy && (a->H != b->H || a->W != b->W))) {
-      r = fs_bn_bwd_apply2(a, nullptr, dtype, stream);
-      return r != FS_OK ? r : fs_bn_bwd_apply2(b, nullptr, dtype, stream);
-    }
-  }
+  BnPair<FsBnBwdArgs> pr;
+  int r;
+  if (!bn_pair(a, b, &FsBnBwdArgs::pool_dy, [](const FsBnBwdArgs* x) { return bn_bwd_check(x, true); },
+               [&](const FsBnBwdArgs* x) { return fs_bn_bwd_apply2(x, nullptr, dtype, stream); }, pr, r)) return r;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int vec = dtype == FS_DTYPE_BF16 ? 8 : 4;
-  const int G = a->groups > 1 ? a->groups : 1, G1 = b ? (b->groups > 1 ? b->groups : 1) : 0;
-  long items = (long)(a->M / G) * (a->C / vec);
-  if (b) items = std::max(items, (long)(b->M / G1) * (b->C / vec));
-  const int nslab = a->pool_dy ? 1 : bn_slabs(a->C / vec);
-  dim3 grid(std::min(grid_for(items / nslab), std::max(32, grid_for(1L << 40) / nslab)), nslab, G + G1);
+  const int vec = dtype_lanes(dtype), CG = a->C / vec, nz = pr.G + pr.G1;
+  const int nslab = a->pool_dy ? 1 : bn_slabs(CG);
   const unsigned lds = (a->pool_dy ? 6u : 5u) * (a->C / nslab) * sizeof(float);
-  const FsDual<FsBnBwdArgs, FsNoGeom> d = bn_dual(a, b);
-  const int fast = 1;       // dense tensors take the kernels' fast path (the generic loop serves strided / padded ones)
-  if (a->pool_dy && bn_pool_quads(a->C / vec)) {
-    const int CG = a->C / vec;
-    long Qg = (a->M / G) / 4;
-    if (b) Qg = std::max<long>(Qg, (b->M / G1) / 4);
-    dim3 qgrid((unsigned)std::min<long>((Qg + 256 / CG - 1) / (256 / CG), 2048), 1, G + G1);
-    if (dtype == FS_DTYPE_BF16) hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<bf16>, qgrid, dim3(256), lds, st, d);
-    else if (dtype == FS_DTYPE_F32) hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<float>, qgrid, dim3(256), lds, st, d);
-    else return FS_EINVAL;
-    return fs_launch_status();
+  if (a->pool_dy && bn_pool_quads(CG)) {
+    const dim3 qgrid = quad_grid(pr.larger(quads_per_group<FsBnBwdArgs>), CG, 2048, nz);
+    return by_dtype(dtype, [&](auto e) {
+      hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<typename decltype(e)::type>, qgrid, dim3(256), lds, st, pr.d);
+    });
   }
-  if (a->pool_dy) {
-    if (dtype == FS_DTYPE_BF16) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16, true>), grid, dim3(256), lds, st, d, 0);
-    else if (dtype == FS_DTYPE_F32) hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), grid, dim3(256), lds, st, d, 0);
-    else return FS_EINVAL;
-    return fs_launch_status();
-  }
-  if (dtype == FS_DTYPE_BF16) hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16>, grid, dim3(256), lds, st, d, fast);
-  else if (dtype == FS_DTYPE_F32) hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, grid, dim3(256), lds, st, d, fast);
-  else return FS_EINVAL;
-  return fs_launch_status();
+  const long items = pr.larger([&](const FsBnBwdArgs& x, int G) { return (long)(x.M / G) * (x.C / vec); });
+  dim3 grid(std::min(grid_for(items / nslab), std::max(32, grid_for(1L << 40) / nslab)), nslab, nz);
+  return by_dtype(dtype, [&](auto e) {
+    using T = typename decltype(e)::type;
+    if (a->pool_dy) hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), grid, dim3(256), lds, st, pr.d);
+    else hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), grid, dim3(256), lds, st, pr.d);
+  });
 }
 
 extern "C" int fs_bn_bwd_apply(const FsBnBwdArgs* a, int dtype, void* stream) { return fs_bn_bwd_apply2(a, nullptr, dtype, stream); }

@@ -2,13 +2,12 @@
 // BatchNorm (+ ReLU) in front of a convolution (pro_mode 1), applied to 16-byte units while they travel from the load
 // registers to LDS.  FsConvArgs documents it (include/fsnet_hip.h).  (Mode 2 — the second pass of the backward of the
 // BatchNorm behind the convolution, in the data gradient's staging — existed in rounds 3-4, measured slower and is gone.)  The per-channel coefficients live in a small LDS table that every block fills itself — from
-// the f64 sums the producing kernel's epilogue left (bn_apply_kernel's preamble, bn.hip, same
-// arithmetic: no fs_bn_finalize launch and no BatchNorm pass between two convolutions), or from coefficient arrays
+// the f64 sums the producing kernel's epilogue left (bn_coeffs.h: the arithmetic of bn_apply_kernel's preamble,
+// bn.hip: no fs_bn_finalize launch and no BatchNorm pass between two convolutions), or from coefficient arrays
 // handed in.  Reference: nn.BatchNorm2d in train mode between conv1 and conv2 of a BasicBlock and its autograd
 // backward, vision_base/networks/models/backbone/resnet.py:33-50.
 #pragma once
-#include "common.h"
-#include "fsnet_hip_internal.h"
+#include "bn_coeffs.h"
 
 namespace {
 
@@ -16,25 +15,13 @@ template <int PRO> constexpr int pro_ncoef() { return PRO == 1 ? 2 : 0; }
 // dynamic LDS a launch with this prologue needs
 template <int PRO> inline unsigned pro_lds_bytes(const FsConvArgs& a) { return (unsigned)(pro_ncoef<PRO>() * a.Cs * sizeof(float)); }
 
-__device__ inline void pro_sum_slots(const double* st, int C, int c, double& s1, double& s2) {
-  s1 = 0.0; s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < FS_STAT_SLOTS; ++k) { s1 += st[(long)k * 2 * C + c]; s2 += st[(long)k * 2 * C + C + c]; }
-}
-
-// mode 1, channel c of statistics group g: bn_channel_coeffs of bn.hip
-__device__ inline void pro1_channel(const FsConvArgs& p, int g, int c, float& mean, float& invstd, float& varb,
-                                    float& sc, float& sh) {
+// mode 1, channel c of statistics group g (bn_coeffs.h: the arithmetic bn.hip's kernels use)
+__device__ inline BnCoeffs pro1_channel(const FsConvArgs& p, int g, int c) {
   const int C = p.Cs;
-  double s1, s2;
-  pro_sum_slots(p.pro_stats + (long)g * FS_STAT_SLOTS * 2 * C, C, c, s1, s2);
-  double m = s1 / p.pro_count, v = s2 / p.pro_count - m * m;
-  if (v < 0) v = 0;
-  mean = (float)m;
-  varb = (float)v;
-  invstd = (float)(1.0 / sqrt(v + (double)p.pro_eps));
-  sc = p.pro_gamma[c] * invstd;
-  sh = p.pro_beta[c] - mean * sc;
+  double s1, s2, m, v;
+  bn_sum_slots(p.pro_stats + (long)g * FS_STAT_SLOTS * 2 * C, C, c, s1, s2);
+  bn_moments(s1, s2, p.pro_count, m, v);
+  return bn_coeffs(m, v, p.pro_eps, p.pro_gamma[c], p.pro_beta[c]);
 }
 
 // fills tab[ncoef][Cs] for statistics group grp (all threads of the block; a barrier must follow before it is read)
@@ -43,9 +30,8 @@ __device__ inline void pro_build_table(const FsConvArgs& p, float* tab, int grp,
   const int C = p.Cs;
   if (p.pro_stats) {
     for (int c = t; c < C; c += nt) {
-      float mean, istd, varb, sc, sh;
-      pro1_channel(p, grp, c, mean, istd, varb, sc, sh);
-      tab[c] = sc; tab[C + c] = sh;
+      const BnCoeffs k = pro1_channel(p, grp, c);
+      tab[c] = k.scale; tab[C + c] = k.shift;
     }
   } else {
     for (int c = t; c < C; c += nt) { tab[c] = p.pro_a[grp * C + c]; tab[C + c] = p.pro_b[grp * C + c]; }
@@ -54,7 +40,8 @@ __device__ inline void pro_build_table(const FsConvArgs& p, float* tab, int grp,
 
 // what ONE block of the launch does besides its tile when the coefficients are derived in the kernel: mode 1 — saved
 // statistics, the affine form for the backward's consumers, running statistics (one momentum update per group, in
-// group order, like bn_finalize_kernel)
+// group order: the loop is this function's own because every group's saved state is written on the way, the step is
+// bn_coeffs.h's)
 template <int PRO>
 __device__ inline void pro_block0(const FsConvArgs& p, int t, int nt) {
   if (!p.pro_stats) return;
@@ -65,13 +52,12 @@ __device__ inline void pro_block0(const FsConvArgs& p, int t, int nt) {
     for (int c = t; c < C; c += nt) {
       float rm = track ? p.pro_running_mean[c] : 0.f, rv = track ? p.pro_running_var[c] : 0.f;
       for (int g = 0; g < G; ++g) {
-        float mean, istd, varb, sc, sh;
-        pro1_channel(p, g, c, mean, istd, varb, sc, sh);
-        if (p.pro_mean) { p.pro_mean[g * C + c] = mean; p.pro_invstd[g * C + c] = istd; }
-        if (p.pro_save_a) { p.pro_save_a[g * C + c] = sc; p.pro_save_b[g * C + c] = sh; }
-        const double unb = p.pro_count > 1.0 ? (double)varb * p.pro_count / (p.pro_count - 1.0) : (double)varb;
-        rm = (1.f - p.pro_momentum) * rm + p.pro_momentum * mean;
-        rv = (1.f - p.pro_momentum) * rv + p.pro_momentum * (float)unb;
+        const BnCoeffs k = pro1_channel(p, g, c);
+        if (p.pro_mean) { p.pro_mean[g * C + c] = k.mean; p.pro_invstd[g * C + c] = k.invstd; }
+        if (p.pro_save_a) { p.pro_save_a[g * C + c] = k.scale; p.pro_save_b[g * C + c] = k.shift; }
+        const double unb = bn_unbiased(k.var_b, p.pro_count);
+        rm = bn_momentum(rm, k.mean, p.pro_momentum);
+        rv = bn_momentum(rv, (float)unb, p.pro_momentum);
       }
       if (track) { p.pro_running_mean[c] = rm; p.pro_running_var[c] = rv; }
     }

@@ -244,6 +244,66 @@ def test_batchnorm_and_pool_pairs(dev, dtype):
     assert float((a["rm"][1] - ref_mod.running_mean).abs().max()) < 1e-4
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_batchnorm_pair_of_different_widths(dev, dtype):
+    """fs_bn_apply2 / fs_bn_bwd_reduce2 / fs_bn_bwd_apply2 with two problems that cannot share a launch (32 and 64
+    channels): the library issues them one after the other, == the one-problem calls"""
+    from fsnet_amd.engine.nets import bn_tensors
+    from fsnet_amd.hip import ops
+    from fsnet_amd.hip.conv import run_specs
+    N, H, W = 2, 6, 10
+    g = torch.Generator().manual_seed(7)
+    xs = [torch.randn(N, H, W, Cc, generator=g).to(dev).to(dtype) for Cc in (32, 64)]
+    douts = [torch.randn(x.shape, generator=g).to(dev).to(dtype) for x in xs]
+    bns = []
+    for x in xs:
+        bn = torch.nn.BatchNorm2d(x.shape[-1]).to(dev)
+        bn.weight.data.copy_(torch.rand(x.shape[-1], generator=g) + 0.5); bn.bias.data.copy_(torch.rand(x.shape[-1], generator=g) - 0.5)
+        bns.append(bn)
+    results = {}
+    for mode in ("pair", "solo"):
+        mods = [copy.deepcopy(b) for b in bns]
+        sts = [ops.BnState(x.shape[-1], dev) for x in xs]
+        ys = [torch.empty_like(x) for x in xs]
+        stats = []
+        for x in xs:
+            st = torch.zeros(8, 2, x.shape[-1], dtype=torch.float64, device=dev)
+            v = x.double()
+            st[0, 0] = v.sum((0, 1, 2)); st[0, 1] = (v * v).sum((0, 1, 2))
+            stats.append(st)
+        specs = [ops.bn_apply_spec(x, s_, bn_tensors(m), st, y, H, W, N * H * W, relu=True)
+                 for x, s_, m, st, y in zip(xs, stats, mods, sts, ys)]
+        sums = [torch.zeros(8, 2, x.shape[-1], dtype=torch.float64, device=dev) for x in xs]
+        dxs = [torch.empty_like(x) for x in xs]
+        gouts = [torch.empty_like(x) for x in xs]
+        for m in mods:
+            m.weight.grad = torch.zeros_like(m.weight); m.bias.grad = torch.zeros_like(m.bias)
+        calls = [dict(dout=d, y=y, x=x, gamma=m.weight.data, st=st, dx=dx, dgamma=m.weight.grad, dbeta=m.bias.grad, H=H, W=W,
+                      relu=True, g_out=go, sums=sm) for d, y, x, m, st, dx, go, sm in zip(douts, ys, xs, mods, sts, dxs, gouts, sums)]
+        if mode == "pair":
+            run_specs(specs)
+            ops.bn_backward_multi(calls)
+        else:
+            for sp in specs:
+                run_specs([sp])
+            for c in calls:
+                ops.bn_backward_multi([c])
+        torch.cuda.synchronize()
+        results[mode] = dict(y=ys, dx=dxs, g=gouts, rm=[m.running_mean.clone() for m in mods], rv=[m.running_var.clone() for m in mods],
+                             mean=[st.mean.clone() for st in sts], istd=[st.invstd.clone() for st in sts], sums=[sm.sum(0) for sm in sums],
+                             dg=[m.weight.grad.clone() for m in mods], db=[m.bias.grad.clone() for m in mods],
+                             nbt=[int(m.num_batches_tracked) for m in mods])
+    a, b = results["pair"], results["solo"]
+    assert a["nbt"] == b["nbt"] == [1, 1]
+    for key in ("y", "dx", "g", "rm", "rv", "mean", "istd"):
+        for u, v in zip(a[key], b[key]):
+            assert torch.equal(u, v), key
+    # (the first pass adds into f64 slots in an order the hardware chooses)
+    for key in ("sums", "dg", "db"):
+        for u, v in zip(a[key], b[key]):
+            assert torch.allclose(u, v, rtol=1e-5, atol=1e-5 * float(v.abs().max())), key
+
+
 def _encoders(dev, dtype, norm_eval=False):
     from fsnet_amd.engine.runtime import RT
     from fsnet_amd.vision_base.networks.models.backbone.resnet import resnet

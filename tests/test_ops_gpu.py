@@ -34,11 +34,14 @@ def stats_of(x):  # x NCHW cpu -> [FS_STAT_SLOTS][2][C] with everything in slot 
     return out
 
 
-@pytest.mark.parametrize("mode", ["plain", "res", "res_bn2", "pad_fold"])
-def test_bn_forward_backward(dev, mode):
+# (C = 24: 6 lanes at fp32, not a power of two — the division branches of the index decode, with the strided / padded
+# stores and the folded gradient loads behind them)
+@pytest.mark.parametrize("mode,C", [("plain", 32), ("res", 32), ("res_bn2", 32), ("pad_fold", 32), ("plain", 24), ("pad_fold", 24)],
+                         ids=["plain", "res", "res_bn2", "pad_fold", "plain-24ch", "pad_fold-24ch"])
+def test_bn_forward_backward(dev, mode, C):
     from fsnet_amd.hip import ops
     g = torch.Generator().manual_seed(5)
-    N, C, H, W = 3, 32, 10, 14
+    N, H, W = 3, 10, 14
     x = torch.randn(N, C, H, W, generator=g) * 2 + 0.5
     bn = bn_dict(C, g, dev)
     xr = x.clone().requires_grad_(True)
@@ -180,6 +183,58 @@ def test_bn_bf16_unit(dev):
     assert float((nchw(dx) - xr.grad).norm() / xr.grad.norm()) < 2e-2
     assert float((dg.cpu() - gam.grad).norm() / gam.grad.norm()) < 1e-2
     assert float((db.cpu() - bet.grad).norm() / bet.grad.norm()) < 1e-2
+
+
+def test_bn_eval_mode_coefficients(dev):
+    """no batch statistics (stats None): fs_bn_apply and fs_bn_finalize normalise with the running statistics, which they
+    leave alone — F.batch_norm(training=False)"""
+    from fsnet_amd.hip import ops
+    g = torch.Generator().manual_seed(23)
+    N, C, H, W = 2, 32, 6, 10
+    x = torch.randn(N, C, H, W, generator=g) * 2 + 0.5
+    bn = bn_dict(C, g, dev)
+    bn["running_mean"].copy_(torch.randn(C, generator=g)); bn["running_var"].copy_(torch.rand(C, generator=g) + 0.5)
+    rm, rv = bn["running_mean"].cpu().clone(), bn["running_var"].cpu().clone()
+    y_ref = F.relu(F.batch_norm(x, rm, rv, bn["weight"].cpu(), bn["bias"].cpu(), training=False, eps=1e-5))
+    st = ops.BnState(C, dev)
+    y = torch.empty(N, H, W, C, device=dev)
+    ops.bn_apply(nhwc(x).to(dev), None, bn, st, y, H, W, N * H * W, relu=True)
+    st_f = ops.BnState(C, dev, affine=True)
+    ops.bn_finalize(None, bn, st_f, C, N * H * W)
+    torch.cuda.synchronize()
+    assert (nchw(y) - y_ref).abs().max() < 1e-5
+    y_f = F.relu(x * st_f.scale.cpu().view(1, C, 1, 1) + st_f.shift.cpu().view(1, C, 1, 1))
+    assert (y_f - y_ref).abs().max() < 1e-5
+    assert torch.equal(st.mean, st_f.mean) and torch.equal(st.invstd, st_f.invstd)
+    assert torch.equal(st.mean.cpu(), rm) and torch.allclose(st.invstd.cpu(), (rv + 1e-5).rsqrt(), rtol=1e-6)
+    assert torch.equal(bn["running_mean"].cpu(), rm) and torch.equal(bn["running_var"].cpu(), rv)
+    assert int(bn["num_batches_tracked"]) == 0
+
+
+def test_bn_backward_with_exchanged_sums(dev):
+    """FsBnBwdArgs.sums_local (SyncBN): dx from the exchanged sums, dgamma / dbeta from the local ones.  The stand-in for
+    the exchange is a world of two identical shards — sums and count both double, exactly in f64 — so every result must
+    be the single-device one."""
+    from fsnet_amd.hip import ops
+    g = torch.Generator().manual_seed(29)
+    N, C, H, W = 2, 32, 6, 10
+    x = nhwc(torch.randn(N, C, H, W, generator=g) * 2 + 0.5).to(dev)
+    gy = nhwc(torch.randn(N, C, H, W, generator=g)).to(dev)
+    bn = bn_dict(C, g, dev)
+    st = ops.BnState(C, dev)
+    y = torch.empty_like(x)
+    ops.bn_apply(x, stats_of(nchw(x)).to(dev), bn, st, y, H, W, N * H * W, relu=True)
+    out = {}
+    for world in (1, 2):
+        st.count = float(world * N * H * W)
+        dx, dg, db = torch.empty_like(x), torch.zeros(C, device=dev), torch.zeros(C, device=dev)
+        ops.bn_backward(gy, y, x, bn["weight"], st, dx, dg, db, H, W, relu=True,
+                        allreduce=(lambda s_, out: torch.mul(s_, 2.0, out=out)) if world == 2 else None)
+        torch.cuda.synchronize()
+        out[world] = (dx, dg, db)
+    # (the first pass adds into f64 slots in an order the hardware chooses: one float rounding of room)
+    for u, v in zip(out[1], out[2]):
+        assert float((u - v).abs().max()) <= 1e-6 * float(u.abs().max())
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -520,19 +575,23 @@ def test_overlapped_mask_off_vs_reference_golden(dev):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("N,H,W,G,keep_y,with_add", [(2, 8, 12, 1, True, True), (4, 12, 20, 2, False, False),
-                                                     (3, 96, 64, 1, True, False), (2, 6, 10, 2, True, True)])
-def test_stem_batchnorm_relu_maxpool_in_one_pass(dev, dtype, N, H, W, G, keep_y, with_add):
+@pytest.mark.parametrize("Cc,N,H,W,G,keep_y,with_add",
+                         [(64, 2, 8, 12, 1, True, True), (64, 4, 12, 20, 2, False, False), (64, 3, 96, 64, 1, True, False),
+                          (64, 2, 6, 10, 2, True, True), (24, 2, 6, 10, 2, False, False), (24, 2, 8, 12, 1, True, True)],
+                         ids=["2-8-12-1-True-True", "4-12-20-2-False-False", "3-96-64-1-True-False", "2-6-10-2-True-True",
+                              "24ch-2-6-10-2-False-False", "24ch-2-8-12-1-True-True"])
+def test_stem_batchnorm_relu_maxpool_in_one_pass(dev, dtype, Cc, N, H, W, G, keep_y, with_add):
     """fs_bn_apply with FsBnApplyArgs.pool_y (BatchNorm + ReLU + MaxPool2d(3, 2, 1) of the stem, resnet.py:201-206) ==
     fs_bn_apply followed by fs_maxpool_fwd bit for bit (activation, pooled tensor, argmax codes, saved and running
     statistics); its backward with the pooling gradient gathered inside both BatchNorm-backward passes
     (FsBnBwdArgs.pool_dy; the ReLU mask from the stored activation or, where it was never stored, from the raw
-    convolution output) == fs_maxpool_bwd + the two passes on the materialised gradient, and == torch autograd."""
+    convolution output) == fs_maxpool_bwd + the two passes on the materialised gradient, and == torch autograd.
+    64 channels are 16 / 8 lanes of 16 bytes (the backward by 2 x 2 quads); 24 channels are 6 / 3 lanes, not a power of
+    two: the per-pixel gather of the backward and the division branch of the forward (fs_maxpool_* take that width)."""
     import copy
     import torch.nn.functional as F
     from fsnet_amd.engine.nets import bn_tensors
     from fsnet_amd.hip import ops
-    Cc = 64
     g = torch.Generator().manual_seed(11 + H)
     x = torch.randn(N, H, W, Cc, generator=g).to(dev).to(dtype)
     bn0 = torch.nn.BatchNorm2d(Cc).to(dev)
