@@ -18,7 +18,8 @@
 
 namespace {
 
-// fs_conv_wgrad_plan: the launch functions below report (kernel, blocks, threads, resident blocks) instead of launching
+// fs_conv_wgrad_plan: the launch functions below report (kernel, blocks, threads, resident blocks) instead of launching:
+// `if (wg_plan(...)) return 0;` stands where the launch would be
 thread_local int32_t* g_plan = nullptr;
 inline bool wg_plan(int kind, long blocks, int threads, int resident) {
   if (!g_plan) return false;
@@ -26,14 +27,66 @@ inline bool wg_plan(int kind, long blocks, int threads, int resident) {
   return true;
 }
 
-
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+
+// One transposed MFMA operand fragment (bf16, 16x16x32): two ds_read_b64_tr_b16.  Lane (li, lg) addresses an 8-byte row
+// segment of four channels at each of `lo` and `hi` and receives ONE channel of the four pixel rows its 16-lane group
+// addresses, from `lo` in elements 0-3 and from `hi` in 4-7; which rows those are is the calling kernel's choice.
+__device__ __forceinline__ bf16x8 wg_frag(const void* lo, const void* hi) {
+  const s16x4 l = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lo));
+  const s16x4 h = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(hi));
+  const uint2 l2 = __builtin_bit_cast(uint2, l), h2 = __builtin_bit_cast(uint2, h);
+  return __builtin_bit_cast(bf16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
+}
+
+// offset of dW[co][ci][r][s] in the OIHW gradient the optimizer consumes
+__device__ __forceinline__ long wg_oihw(int co, int ci, int r, int s, int Ci, int R, int S) { return (((long)co * Ci + ci) * R + r) * S + s; }
+// GEMM column `col` -> (ci, r, s) through ktab (one entry per group of eg channels: c | r << 16 | s << 24); false for
+// the K padding and for the padded input channels (ci >= Ci).  col / eg < ncolgroups is the caller's to know.
+__device__ __forceinline__ bool wg_col(const FsWgradArgs& p, int col, int eg, int& ci, int& r, int& s) {
+  const int e = p.ktab[col / eg];
+  ci = (e & 0xffff) + col % eg; r = (e >> 16) & 0xff; s = (e >> 24) & 0x7f;
+  return e >= 0 && ci < p.Ci;
+}
+// the reduce kernels' last step: dW[co][column col] += v
+__device__ __forceinline__ void wg_dw_add(const FsWgradArgs& p, int co, int col, int eg, float v) {
+  int ci, r, s;
+  if (wg_col(p, col, eg, ci, r, s)) p.dw[wg_oihw(co, ci, r, s, p.Ci, p.R, p.S)] += v;
+}
+
+// Epilogue of an acc[TA][TB] tile whose D rows are co (row0 + a*16 + j, row0 including the lane's lg*4) and whose D
+// column is one GEMM column per lane (col0 + b*16, col0 including the lane's li).  col_off(col) gives the column's
+// offset inside a row of dst, negative to drop it.  ADD = false: a dense split-K slab (every row exists); ADD = true:
+// the unsplit tile, a plain read-modify-write on the rows below `rows` of dW (the block is their sole owner).
+template <bool ADD, int TA, int TB, typename F>
+__device__ __forceinline__ void wg_tile_out(const f32x4 (&acc)[TA][TB], float* dst, long row_stride, int rows, int row0, int col0, F col_off) {
+#pragma unroll
+  for (int b = 0; b < TB; ++b) {
+    const long c = col_off(col0 + b * 16);
+    if (c < 0) continue;
+#pragma unroll
+    for (int a = 0; a < TA; ++a)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int row = row0 + a * 16 + j;
+        if (!ADD) dst[(long)row * row_stride + c] = acc[a][b][j];
+        else if (row < rows) dst[(long)row * row_stride + c] += acc[a][b][j];
+      }
+  }
+}
 
 struct WgDiv { FsDiv dW, dH; };
 
 // Two problems per launch (fsnet_hip_internal.h, FsDual) in every kernel of this file: the pixel splits of both stack
 // along blockIdx.z (the persistent stem kernel: along blockIdx.x), [0, nb0) belong to the first argument set; each
 // problem has its own slab region of the workspace and its own dW.
+// The decode — `prob`, `p`, the geometry, the block's index `zb` among its problem's blocks — is spelled out in each of
+// the four kernels: behind a helper (even one that only reads nb0 and returns `prob`) the compiler addresses the kernarg
+// pair through one computed base instead of a select per field, which is fewer scalar instructions (halo kernel: 107 fewer
+// before its first MFMA) but re-schedules every main loop (halo: 515 -> 502 instructions between the first barrier and the last
+// MFMA, other registers throughout).  This file changes no main loop, so the parent's text stays (bn.hip's bn_problem
+// met the opposite reaction: DESIGN.md section 21).
+
 template <typename T, int COT, int CLT, int WR, int CH>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const FsDual<FsWgradArgs, WgDiv> d) {
   const int prob = (int)blockIdx.z >= d.nb0 ? 1 : 0;
@@ -149,18 +202,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const FsDual<FsWgradArg
 #pragma unroll
       for (int a = 0; a < TA; ++a) {
         const T* base = &lds_a[buf][(ks * 32 + lg * 8 + (li >> 2)) * SA + wr * WROW + a * 16 + (li & 3) * 4];
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + 4 * SA));
-        uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-        fa[a] = __builtin_bit_cast(bf16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
+        fa[a] = wg_frag(base, base + 4 * SA);
       }
 #pragma unroll
       for (int b = 0; b < TB; ++b) {
         const T* base = &lds_b[buf][(ks * 32 + lg * 8 + (li >> 2)) * SB + wcn * WCOL + b * 16 + (li & 3) * 4];
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + 4 * SB));
-        uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-        fb[b] = __builtin_bit_cast(bf16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
+        fb[b] = wg_frag(base, base + 4 * SB);
       }
 #pragma unroll
       for (int a = 0; a < TA; ++a)
@@ -189,40 +236,17 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const FsDual<FsWgradArg
   }
 
   // ---- epilogue: D rows = co (lg*4+j), cols = gemm column (li) ----
+  const int row0 = co0 + wr * WROW + lg * 4, lcol0 = col0 + wcn * WCOL + li;
   if (p.nsplit > 1) {
     // split-K partial: dense slab [split][Cd_t][ncols_t] in the workspace (reduced by wgrad_reduce_kernel)
-    float* ws = p.workspace + (long)zb * p.ws_rows * p.ws_cols;
-#pragma unroll
-    for (int b = 0; b < TB; ++b) {
-      int col = col0 + wcn * WCOL + b * 16 + li;
-#pragma unroll
-      for (int a = 0; a < TA; ++a)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          int co = co0 + wr * WROW + a * 16 + lg * 4 + j;
-          ws[(long)co * p.ws_cols + col] = acc[a][b][j];
-        }
-    }
+    wg_tile_out<false>(acc, p.workspace + (long)zb * p.ws_rows * p.ws_cols, p.ws_cols, 0, row0, lcol0, [](int col) { return (long)col; });
     return;
   }
-#pragma unroll
-  for (int b = 0; b < TB; ++b) {
-    int col = col0 + wcn * WCOL + b * 16 + li;
-    int kg = col / EG;
-    if (kg >= p.ncolgroups) continue;
-    int e = p.ktab[kg];
-    if (e < 0) continue;
-    int ci = (e & 0xffff) + (col % EG);
-    int r = (e >> 16) & 0xff, s = (e >> 24) & 0x7f;
-    if (ci >= p.Ci) continue;
-#pragma unroll
-    for (int a = 0; a < TA; ++a)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        int co = co0 + wr * WROW + a * 16 + lg * 4 + j;
-        if (co < p.Co) p.dw[(((long)co * p.Ci + ci) * p.R + r) * p.S + s] += acc[a][b][j];  // sole owner: plain RMW
-      }
-  }
+  // (the column decoded once, its rows co * Ci*R*S apart)
+  wg_tile_out<true>(acc, p.dw, (long)p.Ci * p.R * p.S, p.Co, row0, lcol0, [&](int col) {
+    int ci, r, s;
+    return col / EG < p.ncolgroups && wg_col(p, col, EG, ci, r, s) ? wg_oihw(0, ci, r, s, p.Ci, p.R, p.S) : -1L;
+  });
 }
 
 // Slab reductions take the two problems of a shared launch in one launch (blockIdx.z).  (Round 5 also had a batched form —
@@ -275,14 +299,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const WgMulti d, int 
     float v = 0.f;
 #pragma unroll
     for (int l = 0; l < 16; l += 4) v += (r[l * 64] + r[(l + 1) * 64]) + (r[(l + 2) * 64] + r[(l + 3) * 64]);
-    int e = p.ktab[col / eg];
-    if (e >= 0) {
-      int ci = (e & 0xffff) + (col % eg);
-      if (ci < p.Ci) {
-        int r2 = (e >> 16) & 0xff, s2 = (e >> 24) & 0x7f;
-        p.dw[(((long)co * p.Ci + ci) * p.R + r2) * p.S + s2] += v;
-      }
-    }
+    wg_dw_add(p, co, col, eg, v);
   }
 }
 
@@ -312,14 +329,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce4_kernel(const WgMulti d, int
   __syncthreads();
   if (zl == 0 && col < ncols) {
     float v = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    int e = p.ktab[col / eg];
-    if (e >= 0) {
-      int ci = (e & 0xffff) + (col % eg);
-      if (ci < p.Ci) {
-        int r = (e >> 16) & 0xff, s = (e >> 24) & 0x7f;
-        p.dw[(((long)co * p.Ci + ci) * p.R + r) * p.S + s] += v;
-      }
-    }
+    wg_dw_add(p, co, col, eg, v);
   }
 }
 
@@ -338,14 +348,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_flat_kernel(const WgMulti d,
 #pragma unroll
   for (int z = 0; z < 8; ++z) v[z] = z < p.nsplit ? ws[(long)z * slab] : 0.f;
   float acc = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-  int e = p.ktab[col / eg];
-  if (e >= 0) {
-    int ci = (e & 0xffff) + (col % eg);
-    if (ci < p.Ci) {
-      int r = (e >> 16) & 0xff, s = (e >> 24) & 0x7f;
-      p.dw[(((long)co * p.Ci + ci) * p.R + r) * p.S + s] += acc;
-    }
-  }
+  wg_dw_add(p, co, col, eg, acc);
 }
 
 // 3x3 slabs in tap-major column order (col = tap*Cs + ci), few splits: a block owns one co x 32 ci x 9 taps.  It
@@ -384,39 +387,21 @@ __global__ __launch_bounds__(320) void wgrad_reduce3x3_kernel(const WgMulti d, i
   }
 }
 
-enum { RK_3X3 = 0, RK_FLAT = 1, RK_4 = 2, RK_16 = 3 };
-struct WgPending { FsWgradArgs a; int kind, eg, gx, gy; };
-
-void launch_reduce_group(const WgPending* it, int n, hipStream_t st) {
-  WgMulti d;
-  int gx = 1, gy = 1;
-  for (int i = 0; i < WG_MULTI; ++i) d.a[i] = it[i < n ? i : 0].a;
-  for (int i = 0; i < n; ++i) { gx = std::max(gx, it[i].gx); gy = std::max(gy, it[i].gy); }
-  const int eg = it[0].eg;
-  switch (it[0].kind) {
-    case RK_3X3: hipLaunchKernelGGL(wgrad_reduce3x3_kernel, dim3(gx, gy, n), dim3(320), 0, st, d, eg); break;
-    case RK_FLAT: hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3(gx, 1, n), dim3(256), 0, st, d, eg); break;
-    case RK_4: hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(gx, 1, n), dim3(256), 0, st, d, eg); break;
-    default: hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(gx, 1, n), dim3(256), 0, st, d, eg); break;
-  }
-}
-
 // b: the launch's (filled-in) arguments; b2 != nullptr: the second problem's, same dW shape — one reduce launch for both
 // (blockIdx.z = problem).  A problem that was not split (nsplit == 1) accumulated into its dW directly.
 void launch_reduce(const FsWgradArgs& b, const FsWgradArgs* b2, int Co, int ncols, int eg, hipStream_t st, bool always = false) {
-  WgPending it[2];
+  WgMulti d;
   int n = 0, ns = 0;
-  if (b.nsplit > 1 || always) { it[n++].a = b; ns = std::max(ns, b.nsplit); }
-  if (b2 && (b2->nsplit > 1 || always)) { it[n++].a = *b2; ns = std::max(ns, b2->nsplit); }
+  if (b.nsplit > 1 || always) { d.a[n++] = b; ns = std::max(ns, b.nsplit); }
+  if (b2 && (b2->nsplit > 1 || always)) { d.a[n++] = *b2; ns = std::max(ns, b2->nsplit); }
   if (n == 0) return;
+  for (int i = n; i < WG_MULTI; ++i) d.a[i] = d.a[0];
   const bool tapmajor3x3 = b.R == 3 && b.S == 3 && ncols % 9 == 0 && (ncols / 9) % 32 == 0;
-  int kind, gx, gy = 1;
-  if (tapmajor3x3 && ns <= 16 && ncols >= 9 * 64) { kind = RK_3X3; gx = ncols / 9 / 32; gy = Co; }
-  else if (ns <= 8 && ncols >= 256) { kind = RK_FLAT; gx = Co * ((ncols + 255) / 256); }
-  else if (ns < 32) { kind = RK_4; gx = Co * ((ncols + 63) / 64); }
-  else { kind = RK_16; gx = Co * ((ncols + 63) / 64); }
-  for (int i = 0; i < n; ++i) { it[i].kind = kind; it[i].eg = eg; it[i].gx = gx; it[i].gy = gy; }
-  launch_reduce_group(it, n, st);
+  const int gx64 = Co * ((ncols + 63) / 64);
+  if (tapmajor3x3 && ns <= 16 && ncols >= 9 * 64) hipLaunchKernelGGL(wgrad_reduce3x3_kernel, dim3(ncols / 9 / 32, Co, n), dim3(320), 0, st, d, eg);
+  else if (ns <= 8 && ncols >= 256) hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3(Co * ((ncols + 255) / 256), 1, n), dim3(256), 0, st, d, eg);
+  else if (ns < 32) hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(gx64, 1, n), dim3(256), 0, st, d, eg);
+  else hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(gx64, 1, n), dim3(256), 0, st, d, eg);
 }
 
 // pixel splits of a launch shared by two problems: `total` slots divided in proportion to their work, at least one each
@@ -442,58 +427,79 @@ int wg_resident_blocks(K kernel, int threads) {
   return cus * per_cu;
 }
 
+// The launchers' argument pair: a[1] repeats a[0] in a one-problem launch; both problems write slabs of ws_rows x ws_cols
+// floats.  The geometry g[], nb0 and the split fields are the launcher's to fill.
+template <typename G>
+FsDual<FsWgradArgs, G> wg_dual(const FsWgradArgs& a, const FsWgradArgs* a2, int ws_rows, int ws_cols) {
+  FsDual<FsWgradArgs, G> d{};
+  d.a[0] = a; d.a[1] = a2 ? *a2 : a;
+  d.nprob = a2 ? 2 : 1;
+  for (FsWgradArgs& b : d.a) { b.ws_rows = ws_rows; b.ws_cols = ws_cols; }
+  return d;
+}
+inline WgDiv wg_divs(const FsWgradArgs& a) { return WgDiv{fs_make_div(a.Wd), fs_make_div(a.Hd)}; }
+
+// Pixel splits of a launch under the workspace rules.  `want`: the splits the kernel would like for its device slots
+// (a pair divides them in proportion to `work`, wg_share); `cap`: each problem's upper bound (enough pixels per block);
+// `slab`: floats of one partial slab.  Without a workspace nothing is split, and what is split fits the workspace; the
+// two problems of a pair share the FIRST problem's workspace: both or neither split.
+struct WgSplits { long s[2]; };
+inline WgSplits wg_plan_splits(const FsWgradArgs& a, bool pair, long want, const long (&work)[2], const long (&cap)[2], long slab) {
+  WgSplits r{{std::min(want, cap[0]), 0}};
+  const long room = a.workspace ? a.workspace_elems / slab : 0;
+  if (pair) {
+    wg_share(want, work[0], work[1], cap[0], cap[1], r.s[0], r.s[1]);
+    if (room < 2) { r.s[0] = 1; r.s[1] = 1; }
+    else if (r.s[0] + r.s[1] > room) { r.s[0] = std::max<long>(1, room * r.s[0] / (r.s[0] + r.s[1])); r.s[1] = std::max<long>(1, room - r.s[0]); }
+  } else {
+    r.s[0] = a.workspace ? std::min(r.s[0], std::max<long>(1, room)) : 1;
+  }
+  return r;
+}
+// the launch's split axis once both nsplit are known: the first problem's blocks come first, the second problem's slab
+// region lies behind the first's.  -> blocks along the split axis
+template <typename G>
+int wg_stack(FsDual<FsWgradArgs, G>& d, long slab) {
+  d.nb0 = d.a[0].nsplit;
+  if (d.nprob < 2) return d.nb0;
+  d.a[1].workspace = d.a[0].workspace ? d.a[0].workspace + (long)d.a[0].nsplit * slab : nullptr;
+  return d.nb0 + d.a[1].nsplit;
+}
+// the GEMM kernels: each problem's pixel range cut into its splits' runs of whole chunks (chunk_pix pixels each), no run
+// empty; then wg_stack
+template <typename G>
+int wg_split_chunks(FsDual<FsWgradArgs, G>& d, const long (&chunks)[2], const WgSplits& sp, int chunk_pix, long slab) {
+  for (int i = 0; i < d.nprob; ++i) {
+    const long cps = (chunks[i] + sp.s[i] - 1) / sp.s[i];
+    d.a[i].pix_per_split = (int)(cps * chunk_pix);
+    d.a[i].nsplit = (int)((chunks[i] + cps - 1) / cps);
+  }
+  return wg_stack(d, slab);
+}
+
 template <typename T, int COT, int CLT, int WR>
 int launch_tile(const FsWgradArgs& a, const FsWgradArgs* a2, hipStream_t st) {
   constexpr int EG = ElemTraits<T>::EG;
   // pixels per pipeline stage: every stage waits one global-load latency, so bf16 tiles that fit the LDS budget
   // take 64 pixels (two MFMA K steps) per stage
   constexpr int CH = (sizeof(T) == 2 && (COT + CLT) <= 192) ? 64 : 32;
-  FsDual<FsWgradArgs, WgDiv> d;
-  FsWgradArgs& b = d.a[0];
-  FsWgradArgs& b2 = d.a[1];
-  b = a; b2 = a2 ? *a2 : a;
-  d.g[0] = WgDiv{fs_make_div(a.Wd), fs_make_div(a.Hd)};
-  d.g[1] = WgDiv{fs_make_div(b2.Wd), fs_make_div(b2.Hd)};
-  d.nprob = a2 ? 2 : 1;
   const int ncols = a.ncolgroups * EG;
   const int ct = (ncols + CLT - 1) / CLT, rt = (a.Cd + COT - 1) / COT;
   const long tiles = (long)ct * rt;
-  const long chunks = (a.M + CH - 1) / CH, chunks2 = a2 ? (a2->M + CH - 1) / CH : 0;
+  FsDual<FsWgradArgs, WgDiv> d = wg_dual<WgDiv>(a, a2, rt * COT, ct * CLT);
+  d.g[0] = wg_divs(d.a[0]); d.g[1] = wg_divs(d.a[1]);
+  const long slab = (long)rt * COT * ct * CLT;
+  const long chunks[2] = {(a.M + CH - 1) / CH, a2 ? (a2->M + CH - 1) / CH : 0};
   // split the pixel (K) range until ~640 blocks are in flight, keeping >= 256 pixels per block and the partial
   // slabs inside the caller's workspace.  (Measured: fewer, longer blocks lose — every stage of the pixel loop
   // waits one global-load latency, so the kernel wants many short chains; the slab traffic is the smaller cost.)
-  long splits = (640 + tiles - 1) / tiles, splits2 = 0;
-  b.ws_rows = rt * COT; b.ws_cols = ct * CLT;
-  b2.ws_rows = b.ws_rows; b2.ws_cols = b.ws_cols;
-  const long slab = (long)b.ws_rows * b.ws_cols;
-  if (a2) {
-    const long cap = std::max<long>(1, chunks / (256 / CH)), cap2 = std::max<long>(1, chunks2 / (256 / CH));
-    wg_share(splits, chunks, chunks2, cap, cap2, splits, splits2);
-    // (the two problems share the first problem's workspace: both or neither split)
-    const long room = a.workspace ? a.workspace_elems / slab : 0;
-    if (room < 2) { splits = 1; splits2 = 1; }
-    else if (splits + splits2 > room) { splits = std::max<long>(1, room * splits / (splits + splits2)); splits2 = std::max<long>(1, room - splits); }
-  } else {
-    splits = std::min<long>(splits, std::max<long>(1, chunks / (256 / CH)));
-    if (!a.workspace) splits = 1;
-    else splits = std::min<long>(splits, std::max<long>(1, a.workspace_elems / slab));
-  }
-  long cps = (chunks + splits - 1) / splits;
-  b.pix_per_split = (int)(cps * CH);
-  b.nsplit = (int)((chunks + cps - 1) / cps);
-  d.nb0 = b.nsplit;
-  int nz = b.nsplit;
-  if (a2) {
-    cps = (chunks2 + splits2 - 1) / splits2;
-    b2.pix_per_split = (int)(cps * CH);
-    b2.nsplit = (int)((chunks2 + cps - 1) / cps);
-    b2.workspace = a.workspace ? a.workspace + (long)b.nsplit * slab : nullptr;
-    nz += b2.nsplit;
-  }
-  dim3 grid(ct, rt, nz);
-  if (g_plan) return wg_plan(0, (long)ct * rt * nz, 256, wg_resident_blocks(conv_wgrad_kernel<T, COT, CLT, WR, CH>, 256)) ? 0 : FS_EINVAL;
-  hipLaunchKernelGGL((conv_wgrad_kernel<T, COT, CLT, WR, CH>), grid, dim3(256), 0, st, d);
-  launch_reduce(b, a2 ? &b2 : nullptr, a.Co, ncols, EG, st);
+  const long cap[2] = {std::max<long>(1, chunks[0] / (256 / CH)), std::max<long>(1, chunks[1] / (256 / CH))};
+  const WgSplits sp = wg_plan_splits(a, a2 != nullptr, (640 + tiles - 1) / tiles, chunks, cap, slab);
+  const int nz = wg_split_chunks(d, chunks, sp, CH, slab);
+  // (the occupancy query only in plan mode: the launch itself does not need it)
+  if (g_plan && wg_plan(0, tiles * nz, 256, wg_resident_blocks(conv_wgrad_kernel<T, COT, CLT, WR, CH>, 256))) return 0;
+  hipLaunchKernelGGL((conv_wgrad_kernel<T, COT, CLT, WR, CH>), dim3(ct, rt, nz), dim3(256), 0, st, d);
+  launch_reduce(d.a[0], a2 ? &d.a[1] : nullptr, a.Co, ncols, EG, st);
   return fs_launch_status();
 }
 
@@ -508,6 +514,18 @@ struct WGeom { int TH, TW, tiles_x, tiles_y, N, Cs, nsplit; unsigned mTW, mHW; F
 
 __device__ __forceinline__ uint4 wg_buf_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
   return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0));
+}
+// the tiled kernels' buffer descriptors over dY (dense [M][Cd] bf16) and x: offsets past the extent (OOB) read as zero
+struct WgRsrc { __amdgpu_buffer_rsrc_t dy, x; };
+__device__ __forceinline__ WgRsrc wg_rsrc(const FsWgradArgs& p) {
+  return WgRsrc{__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.dy), 0, (int)((long)p.M * p.Cd * 2), 0x00020000),
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, (int)p.x_bytes, 0x00020000)};
+}
+// pixel tile `pt` of a tiled kernel -> image n, tile row ty, tile column tx
+struct WgTile { int n, ty, tx; };
+__device__ __forceinline__ WgTile wg_tile(int pt, FsDiv dTX, int tiles_x, FsDiv dTY, int tiles_y) {
+  const int q = fs_div(pt, dTX), tx = pt - q * tiles_x, n = fs_div(q, dTY), ty = q - n * tiles_y;
+  return WgTile{n, ty, tx};
 }
 
 // NG tap groups: NG x 4 waves share the staged tile, group g multiplies only its taps [tap0(g), tap0(g+1)) — the CU
@@ -543,10 +561,7 @@ __global__ __launch_bounds__(256 * NG) void wgrad3x3_halo_kernel(const FsDual<Fs
   const int ci0 = blockIdx.x * CIT, co0 = blockIdx.y * COT;
   const int npix = g.N * g.tiles_y * g.tiles_x;
 
-  const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(p.dy), 0, (int)((long)p.M * p.Cd * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(p.x), 0, (int)p.x_bytes, 0x00020000);
+  const WgRsrc rs = wg_rsrc(p);
 
   // Which pixel a thread stages.  A 16-byte ds_write is served 16 lanes at a time; with the padded row strides (44 / 28
   // dwords) the two (four) consecutive pixels a 16-lane group would write overlap on 12 of the 64 banks.  Within each run
@@ -557,7 +572,12 @@ __global__ __launch_bounds__(256 * NG) void wgrad3x3_halo_kernel(const FsDual<Fs
     const int q16 = q & 15, base = q - q16;
     return U == 8 ? base + (q16 >> 1) + 8 * (q16 & 1) : (U == 4 ? base + (q16 >> 2) + 4 * (q16 & 3) : q);
   };
-  // per-thread load units: tile-relative coordinates are fixed, only (n, y0, x0) changes per tile
+  // per-thread load units: tile-relative coordinates are fixed, only (n, y0, x0) changes per tile.
+  // (This plan, load_regs and store_lds are wgrad3x3_narrow_kernel's with NT = 256, no permutation, co0 = 0 and no
+  // prologue.  One struct template for both — the arrays as members, plan / load / store as forced-inline member
+  // functions — kept scratch, LDS and occupancy, but this kernel took 158 VGPRs for 156 and 24 instructions more, with the
+  // next tile's loads issued in another order inside the main loop; its launches measured 0.3-0.8 % slower and the step
+  // 0.3 %.  So both kernels keep their own text: DESIGN.md section 22.)
   int aty[LA], atx[LA], bhy[LB], bhx[LB];
 #pragma unroll
   for (int i = 0; i < LA; ++i) {
@@ -586,7 +606,8 @@ __global__ __launch_bounds__(256 * NG) void wgrad3x3_halo_kernel(const FsDual<Fs
   float ka[8], kb[8];
   unsigned bok = 0u;                       // which of the thread's x units lie inside the image (padding stays zero)
   auto load_regs = [&](int pt) {
-    int q = fs_div(pt, g.dTX); int tx_i = pt - q * g.tiles_x; int n = fs_div(q, g.dTY); int ty_i = q - n * g.tiles_y;
+    const WgTile tl = wg_tile(pt, g.dTX, g.tiles_x, g.dTY, g.tiles_y);
+    const int n = tl.n;
     if (has_pro) {
       const int pg = p.pro_group_imgs > 0 ? n / p.pro_group_imgs : 0;
       const float* pa = p.pro_a + (long)pg * g.Cs + ci0 + (t % UB) * 8;
@@ -597,20 +618,20 @@ __global__ __launch_bounds__(256 * NG) void wgrad3x3_halo_kernel(const FsDual<Fs
       kb[0] = b0.x; kb[1] = b0.y; kb[2] = b0.z; kb[3] = b0.w; kb[4] = b1.x; kb[5] = b1.y; kb[6] = b1.z; kb[7] = b1.w;
       bok = 0u;
     }
-    int y0 = ty_i * g.TH, x0 = tx_i * g.TW;
+    const int y0 = tl.ty * g.TH, x0 = tl.tx * g.TW;
     // tile origin as 32-bit byte offsets (both tensors are below 2 GiB: the buffer descriptors require it)
     const int abase = (((n * p.Hd + y0) * p.Wd + x0) * p.Cd) * 2;
     const int bbase = (int)(((long)n * p.sN + (long)(y0 - p.pad) * p.sH + (long)(x0 - p.pad) * p.sW) * 2);
 #pragma unroll
     for (int i = 0; i < LA; ++i) {
       const bool ok = aty[i] >= 0 && y0 + aty[i] < p.Hd && x0 + atx[i] < p.Wd;
-      ra[i] = wg_buf_load16(rs_dy, ok ? abase + arel[i] : OOB);
+      ra[i] = wg_buf_load16(rs.dy, ok ? abase + arel[i] : OOB);
     }
 #pragma unroll
     for (int i = 0; i < LB; ++i) {
       const int sy = y0 - p.pad + bhy[i], sx = x0 - p.pad + bhx[i];
       const bool ok = bhy[i] >= 0 && (unsigned)sy < (unsigned)p.Hs && (unsigned)sx < (unsigned)p.Ws;
-      rb[i] = wg_buf_load16(rs_x, ok ? bbase + brel[i] : OOB);
+      rb[i] = wg_buf_load16(rs.x, ok ? bbase + brel[i] : OOB);
       if (has_pro && ok) bok |= 1u << i;
     }
   };
@@ -687,20 +708,14 @@ __global__ __launch_bounds__(256 * NG) void wgrad3x3_halo_kernel(const FsDual<Fs
       bf16x8 fa[TA];
 #pragma unroll
       for (int a = 0; a < TA; ++a) {
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(&lds_a[arow[ks][0] + a * 16]));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(&lds_a[arow[ks][1] + a * 16]));
-        uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-        fa[a] = __builtin_bit_cast(bf16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
+        fa[a] = wg_frag(&lds_a[arow[ks][0] + a * 16], &lds_a[arow[ks][1] + a * 16]);
       }
 #pragma unroll
       for (int tp = 0; tp < TPG; ++tp) {
         if (NG > 1 && tp >= ntap) break;
 #pragma unroll
         for (int b = 0; b < TB; ++b) {
-          s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(&lds_b[brow[ks][0] + toff[tp] + b * 16]));
-          s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(&lds_b[brow[ks][1] + toff[tp] + b * 16]));
-          uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-          bf16x8 fb = __builtin_bit_cast(bf16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
+          bf16x8 fb = wg_frag(&lds_b[brow[ks][0] + toff[tp] + b * 16], &lds_b[brow[ks][1] + toff[tp] + b * 16]);
 #pragma unroll
           for (int a = 0; a < TA; ++a)
             acc[tp][a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb, fa[a], acc[tp][a][b], 0, 0, 0);   // D[ci][co]
@@ -729,7 +744,7 @@ __global__ __launch_bounds__(256 * NG) void wgrad3x3_halo_kernel(const FsDual<Fs
         } else if (co < p.Co) {
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            if (ci + j < p.Ci) p.dw[(((long)co * p.Ci + ci + j) * 3 + tap / 3) * 3 + tap % 3] += v[j];
+            if (ci + j < p.Ci) p.dw[wg_oihw(co, ci + j, tap / 3, tap % 3, p.Ci, 3, 3)] += v[j];
         }
       }
     }
@@ -760,10 +775,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_narrow_kernel(const FsWgradArgs 
   const int ci0 = blockIdx.x * CIT;
   const int npix = g.N * g.tiles_y * g.tiles_x;
 
-  const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(p.dy), 0, (int)((long)p.M * p.Cd * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(p.x), 0, (int)p.x_bytes, 0x00020000);
+  const WgRsrc rs = wg_rsrc(p);
 
   int aty[LA], atx[LA], bhy[LB], bhx[LB];
 #pragma unroll
@@ -788,20 +800,21 @@ __global__ __launch_bounds__(256) void wgrad3x3_narrow_kernel(const FsWgradArgs 
   uint4 ra[LA], rb[LB];
   // (no operand prologue here: launch_wgrad sends every launch that carries one to the halo kernel above)
   auto load_regs = [&](int pt) {
-    int q = fs_div(pt, g.dTX); int tx_i = pt - q * g.tiles_x; int n = fs_div(q, g.dTY); int ty_i = q - n * g.tiles_y;
-    int y0 = ty_i * g.TH, x0 = tx_i * g.TW;
+    const WgTile tl = wg_tile(pt, g.dTX, g.tiles_x, g.dTY, g.tiles_y);
+    const int n = tl.n;
+    const int y0 = tl.ty * g.TH, x0 = tl.tx * g.TW;
     const int abase = (((n * p.Hd + y0) * p.Wd + x0) * p.Cd) * 2;
     const int bbase = (int)(((long)n * p.sN + (long)(y0 - p.pad) * p.sH + (long)(x0 - p.pad) * p.sW) * 2);
 #pragma unroll
     for (int i = 0; i < LA; ++i) {
       const bool ok = aty[i] >= 0 && y0 + aty[i] < p.Hd && x0 + atx[i] < p.Wd;
-      ra[i] = wg_buf_load16(rs_dy, ok ? abase + arel[i] : OOB);
+      ra[i] = wg_buf_load16(rs.dy, ok ? abase + arel[i] : OOB);
     }
 #pragma unroll
     for (int i = 0; i < LB; ++i) {
       const int sy = y0 - p.pad + bhy[i], sx = x0 - p.pad + bhx[i];
       const bool ok = bhy[i] >= 0 && (unsigned)sy < (unsigned)p.Hs && (unsigned)sx < (unsigned)p.Ws;
-      rb[i] = wg_buf_load16(rs_x, ok ? bbase + brel[i] : OOB);
+      rb[i] = wg_buf_load16(rs.x, ok ? bbase + brel[i] : OOB);
     }
   };
   auto store_lds = [&]() {
@@ -845,19 +858,13 @@ __global__ __launch_bounds__(256) void wgrad3x3_narrow_kernel(const FsWgradArgs 
     if (pt + g.nsplit < npix) load_regs(pt + g.nsplit);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(&lds_a[arow[ks][0]]));
-      s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(&lds_a[arow[ks][1]]));
-      uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-      const bf16x8 fa = __builtin_bit_cast(bf16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
+      const bf16x8 fa = wg_frag(&lds_a[arow[ks][0]], &lds_a[arow[ks][1]]);
 #pragma unroll
       for (int tp = 0; tp < 9; ++tp) {
         const int toff = ((tp / 3) * HW + (tp % 3)) * SB;
 #pragma unroll
         for (int b = 0; b < TB; ++b) {
-          s16x4 blo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(&lds_b[brow[ks][0] + toff + b * 16]));
-          s16x4 bhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(&lds_b[brow[ks][1] + toff + b * 16]));
-          uint2 bl = __builtin_bit_cast(uint2, blo), bh = __builtin_bit_cast(uint2, bhi);
-          bf16x8 fb = __builtin_bit_cast(bf16x8, make_uint4(bl.x, bl.y, bh.x, bh.y));
+          bf16x8 fb = wg_frag(&lds_b[brow[ks][0] + toff + b * 16], &lds_b[brow[ks][1] + toff + b * 16]);
           acc[tp][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, acc[tp][b], 0, 0, 0);
         }
       }
@@ -899,7 +906,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_narrow_kernel(const FsWgradArgs 
         if (g.nsplit > 1) {
           p.workspace[((long)blockIdx.z * p.ws_rows + co) * p.ws_cols + tp * g.Cs + ci] = v;
         } else if (co < p.Co && ci < p.Ci) {
-          p.dw[(((long)co * p.Ci + ci) * 3 + tp / 3) * 3 + tp % 3] += v;
+          p.dw[wg_oihw(co, ci, tp / 3, tp % 3, p.Ci, 3, 3)] += v;
         }
       }
     }
@@ -932,28 +939,25 @@ __global__ __launch_bounds__(256) void wgrad_stem_kernel(const FsDual<FsWgradArg
   __shared__ __attribute__((aligned(16))) T lds_b[PH * PW * 8];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int li = lane & 15, lg = lane >> 4;
-  const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(p.dy), 0, (int)((long)p.M * p.Cd * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(p.x), 0, (int)p.x_bytes, 0x00020000);
+  const WgRsrc rs = wg_rsrc(p);
 
   uint4 ra[LA], rb[LB];
   auto load_regs = [&](int tile) {
-    const int q = fs_div(tile, dTX); const int tx_i = tile - q * tiles_x; const int n = fs_div(q, dTY); const int ty_i = q - n * tiles_y;
-    const int y0 = ty_i * TY, x0 = tx_i * TX;
+    const WgTile tl = wg_tile(tile, dTX, tiles_x, dTY, tiles_y);
+    const int n = tl.n, y0 = tl.ty * TY, x0 = tl.tx * TX;
 #pragma unroll
     for (int i = 0; i < LA; ++i) {
       const int idx = t + i * 256, pix = idx >> 3, u = idx & 7;
       const int y = y0 + (pix >> 4), x = x0 + (pix & 15);
       const bool ok = y < p.Hd && x < p.Wd;
-      ra[i] = wg_buf_load16(rs_dy, ok ? (int)((((long)n * p.Hd + y) * p.Wd + x) * p.Cd + u * 8) * 2 : OOB);
+      ra[i] = wg_buf_load16(rs.dy, ok ? (int)((((long)n * p.Hd + y) * p.Wd + x) * p.Cd + u * 8) * 2 : OOB);
     }
 #pragma unroll
     for (int i = 0; i < LB; ++i) {
       const int idx = t + i * 256, py = idx / PW, px = idx - py * PW;
       const int sy = 2 * y0 - 3 + py, sx = 2 * x0 - 3 + px;
       const bool ok = idx < PH * PW && (unsigned)sy < (unsigned)p.Hs && (unsigned)sx < (unsigned)p.Ws;
-      rb[i] = wg_buf_load16(rs_x, ok ? (int)(((long)n * p.sN + (long)sy * p.sH + (long)sx * p.sW) * 2) : OOB);
+      rb[i] = wg_buf_load16(rs.x, ok ? (int)(((long)n * p.sN + (long)sy * p.sH + (long)sx * p.sW) * 2) : OOB);
     }
   };
   auto store_lds = [&]() {
@@ -999,19 +1003,13 @@ __global__ __launch_bounds__(256) void wgrad_stem_kernel(const FsDual<FsWgradArg
       bf16x8 fa[4];
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(&lds_a[arow[ks][0] + a * 16]));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(&lds_a[arow[ks][1] + a * 16]));
-        uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-        fa[a] = __builtin_bit_cast(bf16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
+        fa[a] = wg_frag(&lds_a[arow[ks][0] + a * 16], &lds_a[arow[ks][1] + a * 16]);
       }
 #pragma unroll
       for (int c = 0; c < 7; ++c) {
         const int ct = wave * 7 + c;                         // column tile: kernel row ct / 4, tap pair ct % 4
         const int toff = ((ct >> 2) * PW + 2 * (ct & 3)) * 8;
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(&lds_b[brow[ks][0] + toff]));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(&lds_b[brow[ks][1] + toff]));
-        uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-        const bf16x8 fb = __builtin_bit_cast(bf16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
+        const bf16x8 fb = wg_frag(&lds_b[brow[ks][0] + toff], &lds_b[brow[ks][1] + toff]);
 #pragma unroll
         for (int a = 0; a < 4; ++a) acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb, acc[a][c], 0, 0, 0);
       }
@@ -1053,58 +1051,45 @@ WGeom wgrad_pick_geom(int Hd, int Wd) {
 
 template <int COT, int CIT>
 int launch_wgrad_halo_t(const FsWgradArgs& a, const FsWgradArgs* a2, hipStream_t st) {
-  FsDual<FsWgradArgs, WGeom> d;
-  FsWgradArgs& b = d.a[0];
-  FsWgradArgs& b2 = d.a[1];
-  b = a; b2 = a2 ? *a2 : a;
-  d.nprob = a2 ? 2 : 1;
   const int Cs = a.ncolgroups * 8 / 9;
+  FsDual<FsWgradArgs, WGeom> d = wg_dual<WGeom>(a, a2, a.Cd, 9 * Cs);
   WGeom& g = d.g[0];
   g = wgrad_pick_geom(a.Hd, a.Wd);
   if (g.TH == 0) return FS_EINVAL;
   g.N = a.M / (a.Hd * a.Wd); g.Cs = Cs;
   d.g[1] = g;
-  d.g[1].N = b2.M / (b2.Hd * b2.Wd);
+  d.g[1].N = d.a[1].M / (d.a[1].Hd * d.a[1].Wd);
   const int out_tiles = (a.Cd / COT) * (Cs / CIT);
-  const int npix = g.N * g.tiles_x * g.tiles_y, npix2 = a2 ? d.g[1].N * g.tiles_x * g.tiles_y : 0;
-  b.ws_rows = a.Cd; b.ws_cols = 9 * Cs;
-  b2.ws_rows = b.ws_rows; b2.ws_cols = b.ws_cols;
-  const long slab = (long)b.ws_rows * b.ws_cols;
+  const long npix[2] = {g.N * g.tiles_x * g.tiles_y, a2 ? d.g[1].N * g.tiles_x * g.tiles_y : 0};
+  const long slab = (long)a.Cd * 9 * Cs;
   // one round of resident blocks: every split adds a Cd x 9Cs fp32 slab to write and re-read, every block beyond the
-  // resident ones waits for a whole block to finish
+  // resident ones waits for a whole block to finish.  (A pair: both problems in the one round, the device's slots
+  // divided by their pixel tiles; one shared slab arena, a's.)
   static const int slots = wg_resident_blocks(wgrad3x3_halo_kernel<COT, CIT, 2>, 512);
-  long splits, splits2 = 0;
-  if (a2) {
-    // both problems in the one round: the device's slots divided by their pixel tiles; one shared slab arena (a's)
-    wg_share(std::max(2, slots / out_tiles), npix, npix2, std::max(1, npix / 2), std::max(1, npix2 / 2), splits, splits2);
-    const long room = a.workspace ? a.workspace_elems / slab : 0;
-    if (room < 2) { splits = 1; splits2 = 1; }
-    else if (splits + splits2 > room) { splits = std::max<long>(1, room * splits / (splits + splits2)); splits2 = std::max<long>(1, room - splits); }
-  } else {
-    splits = std::max<long>(1, std::min<long>(npix / 2 > 0 ? npix / 2 : 1, std::max(1, slots / out_tiles)));
-    if (!a.workspace) splits = 1;
-    else splits = std::min<long>(splits, std::max<long>(1, a.workspace_elems / slab));
-  }
-  g.nsplit = (int)splits; b.nsplit = g.nsplit;
-  d.nb0 = g.nsplit;
-  int nz = g.nsplit;
-  if (a2) {
-    d.g[1].nsplit = (int)splits2; b2.nsplit = (int)splits2;
-    b2.workspace = a.workspace ? a.workspace + (long)b.nsplit * slab : nullptr;
-    nz += (int)splits2;
-  }
+  const long cap[2] = {std::max<long>(1, npix[0] / 2), std::max<long>(1, npix[1] / 2)};
+  const WgSplits sp = wg_plan_splits(a, a2 != nullptr, std::max(1, slots / out_tiles), npix, cap, slab);
+  for (int i = 0; i < d.nprob; ++i) { d.g[i].nsplit = (int)sp.s[i]; d.a[i].nsplit = (int)sp.s[i]; }   // (tile pt of block z: z, z + nsplit, ...)
+  const int nz = wg_stack(d, slab);
   dim3 grid(Cs / CIT, a.Cd / COT, nz);
   // two tap groups: one, three and four measured — 35.0 / 30.3 / 30.3 / 30.1 us at 288 blocks, 25.0 / 22.9 / - / 22.5 us
   // at 256 (64 -> 64 @48x160 B=12, with the reduce); in the step four groups (1024-thread blocks) lose to two
   if (wg_plan(1, (long)grid.x * grid.y * grid.z, 512, slots)) return 0;
   hipLaunchKernelGGL((wgrad3x3_halo_kernel<COT, CIT, 2>), grid, dim3(512), 0, st, d);
-  launch_reduce(b, a2 ? &b2 : nullptr, a.Co, 9 * Cs, 8, st);
+  launch_reduce(d.a[0], a2 ? &d.a[1] : nullptr, a.Co, 9 * Cs, 8, st);
   return fs_launch_status();
 }
 
 int launch_wgrad_halo(const FsWgradArgs& a, const FsWgradArgs* a2, hipStream_t st) {
   // (32 x 32 tiles — twice the tiles, half the pixel splits and slabs — measured 0.5-1 % slower end to end)
   return launch_wgrad_halo_t<64, 32>(a, a2, st);
+}
+
+// an instantiation of the narrow kernel and the blocks of it the device holds at once (asked once per process)
+struct WgNarrow { void (*kernel)(FsWgradArgs, WGeom); int slots; };
+template <int COT, int CIT>
+WgNarrow wg_narrow() {
+  static const int slots = wg_resident_blocks(wgrad3x3_narrow_kernel<COT, CIT>, 256);
+  return WgNarrow{wgrad3x3_narrow_kernel<COT, CIT>, slots};
 }
 
 int launch_wgrad_narrow(const FsWgradArgs& a, hipStream_t st) {
@@ -1121,36 +1106,26 @@ int launch_wgrad_narrow(const FsWgradArgs& a, hipStream_t st) {
   const long slab = (long)b.ws_rows * b.ws_cols;
   // every tile step waits one global-load latency: as many short chains as the device holds at once (2-4 blocks per
   // CU by the instantiation's registers) — one round, see wg_resident_blocks; the slabs are tiny (16 x 9Cs floats)
-  static const int slots_32_32 = wg_resident_blocks(wgrad3x3_narrow_kernel<32, 32>, 256);
-  static const int slots_16_32 = wg_resident_blocks(wgrad3x3_narrow_kernel<16, 32>, 256);
-  static const int slots_16_16 = wg_resident_blocks(wgrad3x3_narrow_kernel<16, 16>, 256);
-  const int slots = COT == 32 ? slots_32_32 : CIT == 32 ? slots_16_32 : slots_16_16;
-  long splits = std::max<long>(1, std::min<long>(npix / 4 > 0 ? npix / 4 : 1, std::max(1, slots / out_tiles)));
-  if (!a.workspace) splits = 1;
-  else splits = std::min<long>(splits, std::max<long>(1, a.workspace_elems / slab));
-  g.nsplit = (int)splits; b.nsplit = g.nsplit;
+  const WgNarrow k = COT == 32 && CIT == 32 ? wg_narrow<32, 32>() : COT == 16 && CIT == 32 ? wg_narrow<16, 32>() :
+                     COT == 16 && CIT == 16 ? wg_narrow<16, 16>() : WgNarrow{nullptr, 0};
+  if (!k.kernel) return FS_EINVAL;
+  const long work[2] = {npix, 0}, cap[2] = {std::max(1, npix / 4), 0};
+  g.nsplit = (int)wg_plan_splits(a, false, std::max(1, k.slots / out_tiles), work, cap, slab).s[0]; b.nsplit = g.nsplit;
   dim3 grid(out_tiles, 1, g.nsplit);
-  if (wg_plan(2, (long)grid.x * grid.z, 256, slots)) return (COT == 32 && CIT == 32) || (COT == 16 && (CIT == 32 || CIT == 16)) ? 0 : FS_EINVAL;
-  if (COT == 32 && CIT == 32) hipLaunchKernelGGL((wgrad3x3_narrow_kernel<32, 32>), grid, dim3(256), 0, st, b, g);
-  else if (COT == 16 && CIT == 32) hipLaunchKernelGGL((wgrad3x3_narrow_kernel<16, 32>), grid, dim3(256), 0, st, b, g);
-  else if (COT == 16 && CIT == 16) hipLaunchKernelGGL((wgrad3x3_narrow_kernel<16, 16>), grid, dim3(256), 0, st, b, g);
-  else return FS_EINVAL;
+  if (wg_plan(2, (long)grid.x * grid.z, 256, k.slots)) return 0;
+  hipLaunchKernelGGL(k.kernel, grid, dim3(256), 0, st, b, g);
   launch_reduce(b, nullptr, a.Co, 9 * Cs, 8, st);
   return fs_launch_status();
 }
 
 int launch_wgrad_stem(const FsWgradArgs& a, const FsWgradArgs* a2, hipStream_t st) {
-  FsDual<FsWgradArgs, StemGeom> d;
+  FsDual<FsWgradArgs, StemGeom> d = wg_dual<StemGeom>(a, a2, 64, 49 * 8);
   FsWgradArgs& b = d.a[0];
   FsWgradArgs& b2 = d.a[1];
-  b = a; b2 = a2 ? *a2 : a;
-  d.nprob = a2 ? 2 : 1;
   const int tiles_x = (a.Wd + 15) / 16, tiles_y = (a.Hd + 7) / 8;
   const long ntiles = (long)(a.M / (a.Hd * a.Wd)) * tiles_x * tiles_y;
   const long ntiles2 = a2 ? (long)(a2->M / (a2->Hd * a2->Wd)) * tiles_x * tiles_y : 0;
-  b.ws_rows = 64; b.ws_cols = 49 * 8;
-  b2.ws_rows = 64; b2.ws_cols = 49 * 8;
-  const long slab = (long)b.ws_rows * b.ws_cols;
+  const long slab = 64 * 49 * 8;
   // one slab per persistent block (100 KB each, written and re-read), as many blocks as the device holds at once
   static const int slots = wg_resident_blocks(wgrad_stem_kernel, 256);   // (320 blocks of this one-block-per-CU kernel ran as two rounds)
   const long max_blocks = std::min<long>(slots, a.workspace_elems / slab);
@@ -1162,16 +1137,12 @@ int launch_wgrad_stem(const FsWgradArgs& a, const FsWgradArgs* a2, hipStream_t s
   b.nsplit = blocks;
   d.g[0] = StemGeom{tiles_x, tiles_y, (int)ntiles, per, fs_make_div(tiles_x), fs_make_div(tiles_y)};
   d.g[1] = d.g[0];
-  d.nb0 = blocks;
-  int total = blocks;
   if (a2) {
     const int per2 = (int)((ntiles2 + mb2 - 1) / mb2);
-    const int blocks2 = (int)((ntiles2 + per2 - 1) / per2);
-    b2.nsplit = blocks2;
-    b2.workspace = a.workspace + (long)blocks * slab;
+    b2.nsplit = (int)((ntiles2 + per2 - 1) / per2);
     d.g[1].ntiles = (int)ntiles2; d.g[1].tiles_per_block = per2;
-    total += blocks2;
   }
+  const int total = wg_stack(d, slab);      // (the workspace exists: wgrad_path)
   if (wg_plan(3, total, 256, slots)) return 0;
   hipLaunchKernelGGL(wgrad_stem_kernel, dim3(total), dim3(256), 0, st, d);
   // (the persistent blocks always leave slabs, also a single one)
@@ -1289,17 +1260,11 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_kernel(const FsDual<FsWgradAr
     bf16x8 fa[TA], fb[TB];
 #pragma unroll
     for (int a = 0; a < TA; ++a) {
-      s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sb + fa_off[a]));
-      s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sb + fa_off[a] + 4 * RBA));
-      uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-      fa[a] = __builtin_bit_cast(bf16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
+      fa[a] = wg_frag(sb + fa_off[a], sb + fa_off[a] + 4 * RBA);
     }
 #pragma unroll
     for (int b = 0; b < TB; ++b) {
-      s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sb + fb_off[b]));
-      s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sb + fb_off[b] + 4 * RBB));
-      uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-      fb[b] = __builtin_bit_cast(bf16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
+      fb[b] = wg_frag(sb + fb_off[b], sb + fb_off[b] + 4 * RBB);
     }
 #pragma unroll
     for (int a = 0; a < TA; ++a)
@@ -1311,89 +1276,47 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_kernel(const FsDual<FsWgradAr
   }
 
   // ---- epilogue: D rows = co (lg*4 + j), columns = ci (li) ----
+  const int row0 = co0 + wr * WROW + lg * 4, lcol0 = ci0 + wcn * WCOL + li;
   if (p.nsplit > 1) {
-    float* ws = p.workspace + (long)zb * p.ws_rows * p.ws_cols;
-#pragma unroll
-    for (int b = 0; b < TB; ++b) {
-      const int col = ci0 + wcn * WCOL + b * 16 + li;
-#pragma unroll
-      for (int a = 0; a < TA; ++a)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int co = co0 + wr * WROW + a * 16 + lg * 4 + j;
-          ws[(long)co * p.ws_cols + col] = acc[a][b][j];
-        }
-    }
+    wg_tile_out<false>(acc, p.workspace + (long)zb * p.ws_rows * p.ws_cols, p.ws_cols, 0, row0, lcol0, [](int col) { return (long)col; });
     return;
   }
-#pragma unroll
-  for (int b = 0; b < TB; ++b) {
-    const int ci = ci0 + wcn * WCOL + b * 16 + li;
-    if (ci >= p.Ci) continue;
-#pragma unroll
-    for (int a = 0; a < TA; ++a)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int co = co0 + wr * WROW + a * 16 + lg * 4 + j;
-        if (co < p.Co) p.dw[(long)co * p.Ci + ci] += acc[a][b][j];      // sole owner: plain RMW
-      }
-  }
+  // (1x1: the column IS the input channel — no ktab load here)
+  const int Ci = p.Ci;
+  wg_tile_out<true>(acc, p.dw, Ci, p.Co, row0, lcol0, [Ci](int ci) { return ci < Ci ? (long)ci : -1L; });
 }
 
 template <int COT, int CIT>
 int launch_w1(const FsWgradArgs& a, const FsWgradArgs* a2, hipStream_t st) {
   constexpr int NST = 4;
-  FsDual<FsWgradArgs, WgDiv> d;
-  FsWgradArgs& b = d.a[0];
-  FsWgradArgs& b2 = d.a[1];
-  b = a; b2 = a2 ? *a2 : a;
-  d.g[0] = WgDiv{fs_make_div(a.Wd), fs_make_div(a.Hd)};
-  d.g[1] = WgDiv{fs_make_div(b2.Wd), fs_make_div(b2.Hd)};
-  d.nprob = a2 ? 2 : 1;
   const int ncols = a.ncolgroups * 8;
   const int ct = (ncols + CIT - 1) / CIT, rt = (a.Cd + COT - 1) / COT;
   const long tiles = (long)ct * rt;
-  const long chunks = (a.M + 31) / 32, chunks2 = a2 ? (a2->M + 31) / 32 : 0;
+  FsDual<FsWgradArgs, WgDiv> d = wg_dual<WgDiv>(a, a2, rt * COT, ct * CIT);
+  d.g[0] = wg_divs(d.a[0]); d.g[1] = wg_divs(d.a[1]);
+  const long slab = (long)rt * COT * ct * CIT;
+  const long chunks[2] = {(a.M + 31) / 32, a2 ? (a2->M + 31) / 32 : 0};
   // one round of resident blocks (two per CU), >= 256 pixels per block, the slabs inside the caller's workspace
   static const int slots = wg_resident_blocks(wgrad1x1_kernel<COT, CIT, NST>, 256);
-  long splits = std::max<long>(1, slots / tiles), splits2 = 0;
-  b.ws_rows = rt * COT; b.ws_cols = ct * CIT;
-  b2.ws_rows = b.ws_rows; b2.ws_cols = b.ws_cols;
-  const long slab = (long)b.ws_rows * b.ws_cols;
-  if (a2) {
-    wg_share(std::max<long>(2, splits), chunks, chunks2, std::max<long>(1, chunks / 8), std::max<long>(1, chunks2 / 8), splits, splits2);
-    const long room = a.workspace ? a.workspace_elems / slab : 0;
-    if (room < 2) { splits = 1; splits2 = 1; }
-    else if (splits + splits2 > room) { splits = std::max<long>(1, room * splits / (splits + splits2)); splits2 = std::max<long>(1, room - splits); }
-  } else {
-    splits = std::min<long>(splits, std::max<long>(1, chunks / 8));
-    if (!a.workspace) splits = 1;
-    else splits = std::min<long>(splits, std::max<long>(1, a.workspace_elems / slab));
-  }
-  long cps = (chunks + splits - 1) / splits;
-  b.pix_per_split = (int)(cps * 32);
-  b.nsplit = (int)((chunks + cps - 1) / cps);
-  d.nb0 = b.nsplit;
-  int nz = b.nsplit;
-  if (a2) {
-    cps = (chunks2 + splits2 - 1) / splits2;
-    b2.pix_per_split = (int)(cps * 32);
-    b2.nsplit = (int)((chunks2 + cps - 1) / cps);
-    b2.workspace = a.workspace ? a.workspace + (long)b.nsplit * slab : nullptr;
-    nz += b2.nsplit;
-  }
-  if (g_plan) return wg_plan(0, tiles * nz, 256, slots) ? 0 : FS_EINVAL;
+  const long cap[2] = {std::max<long>(1, chunks[0] / 8), std::max<long>(1, chunks[1] / 8)};
+  const WgSplits sp = wg_plan_splits(a, a2 != nullptr, std::max<long>(1, slots / tiles), chunks, cap, slab);
+  const int nz = wg_split_chunks(d, chunks, sp, 32, slab);
+  if (wg_plan(0, tiles * nz, 256, slots)) return 0;
   hipLaunchKernelGGL((wgrad1x1_kernel<COT, CIT, NST>), dim3(ct, rt, nz), dim3(256), 0, st, d);
-  launch_reduce(b, a2 ? &b2 : nullptr, a.Co, ncols, 8, st);
+  launch_reduce(d.a[0], a2 ? &d.a[1] : nullptr, a.Co, ncols, 8, st);
   return fs_launch_status();
+}
+
+// both operands are addressable by a 32-bit buffer offset (the bf16 kernels that load through buffer descriptors)
+inline bool wg_fits_32bit(const FsWgradArgs& a) {
+  return a.x_bytes > 0 && a.x_bytes <= 0x7fffffffLL && (long)a.M * a.Cd * 2 <= 0x7fffffffLL;
 }
 
 // 1x1 / pad 0 layers with whole 64-channel tiles on both sides and enough pixels to pipeline
 inline bool w1_takes(const FsWgradArgs& a) {
   const int Cs = a.ncolgroups * 8;
   return a.R == 1 && a.S == 1 && a.pad == 0 && !a.pro_a && a.stride >= 1 && a.Cd % 64 == 0 && Cs % 64 == 0 && a.M >= 2048 &&
-         a.x_bytes > 0 && a.x_bytes <= 0x7fffffffLL && (long)a.M * a.Cd * 2 <= 0x7fffffffLL &&
-         a.sN % 8 == 0 && a.sH % 8 == 0 && a.sW % 8 == 0 && ((uintptr_t)a.dy | (uintptr_t)a.x) % 16 == 0;
+         wg_fits_32bit(a) && a.sN % 8 == 0 && a.sH % 8 == 0 && a.sW % 8 == 0 && ((uintptr_t)a.dy | (uintptr_t)a.x) % 16 == 0;
 }
 inline int launch_wgrad_1x1(const FsWgradArgs& a, const FsWgradArgs* a2, hipStream_t st) {
   const int Cs = a.ncolgroups * 8;
@@ -1404,34 +1327,33 @@ inline int launch_wgrad_1x1(const FsWgradArgs& a, const FsWgradArgs* a2, hipStre
   return launch_w1<64, 64>(a, a2, st);
 }
 
-// which kernel a problem runs on: 1 stem, 2 3x3 LDS-halo, 3 narrow 3x3, 4 / 5 / 6 / 7 / 8 generic tiles, 9 1x1 LDS-DMA, -1 none
+// which kernel a problem runs on (WG_TILE_<COT>: the generic kernel's output-channel tile).  (The plan's `kind` — 0 GEMM
+// kernels, 1 halo, 2 narrow, 3 stem — is a coarser numbering of its own and part of the ABI.)
+enum WgPath { WG_NONE = -1, WG_STEM = 1, WG_HALO, WG_NARROW, WG_TILE_128, WG_TILE_64W, WG_TILE_64, WG_TILE_32, WG_TILE_16, WG_1X1 };
 template <typename T>
-int wgrad_path(const FsWgradArgs& a) {
+WgPath wgrad_path(const FsWgradArgs& a) {
   constexpr bool kBf16 = sizeof(T) == 2;  // f32 tiles are capped by the 64 KB static LDS limit
   if constexpr (kBf16) {
     const int Cs = a.ncolgroups * 8 / (a.R * a.S);
+    const bool halo3x3 = a.use_halo && a.R == 3 && a.S == 3 && a.stride == 1 && wg_fits_32bit(a);
     if (a.use_halo && a.R == 7 && a.S == 7 && a.stride == 2 && a.pad == 3 && Cs == 8 && a.Cd == 64 && a.Co == 64 &&
-        a.workspace && a.x_bytes > 0 && a.x_bytes <= 0x7fffffffLL && (long)a.M * a.Cd * 2 <= 0x7fffffffLL &&
-        a.M >= 4096 && a.M % (a.Hd * a.Wd) == 0)
-      return 1;
-    if (a.use_halo && a.R == 3 && a.S == 3 && a.stride == 1 && a.Cd % 64 == 0 && Cs % 32 == 0 && a.x_bytes > 0 &&
-        a.x_bytes <= 0x7fffffffLL && (long)a.M * a.Cd * 2 <= 0x7fffffffLL && (a.M >= 1024 || a.pro_a))
-      return 2;                          // (tiny pixel counts: too few tiles to split, the generic kernel wins)
-    if (a.pro_a) return -1;              // only the halo kernel stages x through the prologue
-    if (w1_takes(a)) return 9;
-    if (a.use_halo && a.R == 3 && a.S == 3 && a.stride == 1 && ((a.Cd == 16 && Cs % 16 == 0) || (a.Cd == 32 && Cs % 32 == 0)) &&
-        a.x_bytes > 0 && a.x_bytes <= 0x7fffffffLL && (long)a.M * a.Cd * 2 <= 0x7fffffffLL && a.M >= 4096)
-      return 3;
+        a.workspace && wg_fits_32bit(a) && a.M >= 4096 && a.M % (a.Hd * a.Wd) == 0)
+      return WG_STEM;
+    if (halo3x3 && a.Cd % 64 == 0 && Cs % 32 == 0 && (a.M >= 1024 || a.pro_a))
+      return WG_HALO;                    // (tiny pixel counts: too few tiles to split, the generic kernel wins)
+    if (a.pro_a) return WG_NONE;         // only the halo kernel stages x through the prologue
+    if (w1_takes(a)) return WG_1X1;
+    if (halo3x3 && ((a.Cd == 16 && Cs % 16 == 0) || (a.Cd == 32 && Cs % 32 == 0)) && a.M >= 4096) return WG_NARROW;
     // few pixels, wide dW (deep stages, pose decoder): 128x128 tiles halve the operand re-fetch per MFMA and
     // put 16 MFMAs per wave between barriers (the 64x64 tile: 4)
     const int ncols = a.ncolgroups * 8;
-    if (a.Cd % 128 == 0 && ncols >= 1024 && (long)(a.Cd / 128) * ((ncols + 127) / 128) >= 96) return 4;
-    if (a.Cd % 64 == 0 && ncols >= 256) return 5;
+    if (a.Cd % 128 == 0 && ncols >= 1024 && (long)(a.Cd / 128) * ((ncols + 127) / 128) >= 96) return WG_TILE_128;
+    if (a.Cd % 64 == 0 && ncols >= 256) return WG_TILE_64W;
   }
-  if (a.Cd % 64 == 0) return 6;
-  if (a.Cd % 32 == 0) return 7;
-  if (a.Cd % 16 == 0) return 8;
-  return -1;
+  if (a.Cd % 64 == 0) return WG_TILE_64;
+  if (a.Cd % 32 == 0) return WG_TILE_32;
+  if (a.Cd % 16 == 0) return WG_TILE_16;
+  return WG_NONE;
 }
 
 // everything that selects a kernel, its tiles or the shape of dW must agree; pixel counts, pointers and statistics
@@ -1445,39 +1367,52 @@ inline bool wgrad_pairable(const FsWgradArgs& a, const FsWgradArgs& b) {
 template <typename T>
 int launch_wgrad(const FsWgradArgs& a, const FsWgradArgs* a2, hipStream_t st) {
   constexpr bool kBf16 = sizeof(T) == 2;
-  const int path = wgrad_path<T>(a);
+  const WgPath path = wgrad_path<T>(a);
   if (a2) {
     // (the stem pairs although the two encoders' Ci differ — 3 and 6 real channels of the same 8-channel pixels: dW is
     // written through each problem's own Ci)
-    const bool stem_pair = path == 1 && wgrad_path<T>(*a2) == 1 && a.Hd == a2->Hd && a.Wd == a2->Wd && a.Hs == a2->Hs &&
+    const bool stem_pair = path == WG_STEM && wgrad_path<T>(*a2) == WG_STEM && a.Hd == a2->Hd && a.Wd == a2->Wd && a.Hs == a2->Hs &&
                            a.Ws == a2->Ws && a.sH == a2->sH && a.sW == a2->sW;
-    if (!(stem_pair || (path != 3 && path == wgrad_path<T>(*a2) && wgrad_pairable(a, *a2))) || !a.workspace) {
+    if (!(stem_pair || (path != WG_NARROW && path == wgrad_path<T>(*a2) && wgrad_pairable(a, *a2))) || !a.workspace) {
       const int r = launch_wgrad<T>(a, nullptr, st);
       return r != FS_OK ? r : launch_wgrad<T>(*a2, nullptr, st);
     }
   }
   if constexpr (kBf16) {
-    if (path == 1) return launch_wgrad_stem(a, a2, st);
-    if (path == 2) return launch_wgrad_halo(a, a2, st);
-    if (path == 3) return launch_wgrad_narrow(a, st);
-    if (path == 9) return launch_wgrad_1x1(a, a2, st);
-    if (path == 4) return launch_tile<T, 128, 128, 2>(a, a2, st);
-    if (path == 5) return launch_tile<T, 64, 128, 2>(a, a2, st);
+    switch (path) {
+      case WG_STEM: return launch_wgrad_stem(a, a2, st);
+      case WG_HALO: return launch_wgrad_halo(a, a2, st);
+      case WG_NARROW: return launch_wgrad_narrow(a, st);
+      case WG_1X1: return launch_wgrad_1x1(a, a2, st);
+      case WG_TILE_128: return launch_tile<T, 128, 128, 2>(a, a2, st);
+      case WG_TILE_64W: return launch_tile<T, 64, 128, 2>(a, a2, st);
+      default: break;
+    }
   }
-  if (path == 6) return launch_tile<T, 64, 64, 2>(a, a2, st);
-  if (path == 7) return launch_tile<T, 32, 128, 1>(a, a2, st);
-  if (path == 8) {
-    if constexpr (kBf16) return launch_tile<T, 16, 256, 1>(a, a2, st);
-    else return launch_tile<T, 16, 128, 1>(a, a2, st);
+  switch (path) {
+    case WG_TILE_64: return launch_tile<T, 64, 64, 2>(a, a2, st);
+    case WG_TILE_32: return launch_tile<T, 32, 128, 1>(a, a2, st);
+    case WG_TILE_16: return launch_tile<T, 16, kBf16 ? 256 : 128, 1>(a, a2, st);
+    default: return FS_EINVAL;
   }
-  return FS_EINVAL;
 }
 
-int wgrad_check(const FsWgradArgs* args, int dtype) {
-  if (!args || !args->dy || !args->x || !args->dw || !args->ktab) return FS_EINVAL;
+// what the entry points require of an argument set; the single-problem plan entry does not need the tensors
+int wgrad_check(const FsWgradArgs* args, int dtype, bool need_tensors = true) {
+  if (!args || (need_tensors && (!args->dy || !args->x || !args->dw || !args->ktab))) return FS_EINVAL;
   if (args->M <= 0 || args->ncolgroups <= 0) return FS_EINVAL;
   if (args->pro_a && (!args->pro_b || dtype != FS_DTYPE_BF16)) return FS_EINVAL;
   return FS_OK;
+}
+
+// checked arguments -> the launch, or with `plan` its report (wg_plan)
+int wgrad_run(const FsWgradArgs* args, const FsWgradArgs* a1, int dtype, hipStream_t st, int32_t* plan) {
+  g_plan = plan;
+  int r = FS_EINVAL;
+  if (dtype == FS_DTYPE_BF16) r = launch_wgrad<bf16>(*args, a1, st);
+  else if (dtype == FS_DTYPE_F32) r = launch_wgrad<float>(*args, a1, st);
+  g_plan = nullptr;
+  return r;
 }
 
 }  // namespace
@@ -1486,13 +1421,8 @@ int wgrad_check(const FsWgradArgs* args, int dtype) {
 // two share the device's block slots and the FIRST problem's workspace (slab regions back to back), one reduce launch
 // writes both dW.  Problems that do not agree on the kernel run as two launches.
 extern "C" int fs_conv_wgrad2(const FsWgradArgs* args, const FsWgradArgs* a1, int dtype, void* stream) {
-  int r = wgrad_check(args, dtype);
-  if (r != FS_OK) return r;
-  if (a1 && (r = wgrad_check(a1, dtype)) != FS_OK) return r;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == FS_DTYPE_BF16) return launch_wgrad<bf16>(*args, a1, st);
-  if (dtype == FS_DTYPE_F32) return launch_wgrad<float>(*args, a1, st);
-  return FS_EINVAL;
+  if (wgrad_check(args, dtype) != FS_OK || (a1 && wgrad_check(a1, dtype) != FS_OK)) return FS_EINVAL;
+  return wgrad_run(args, a1, dtype, reinterpret_cast<hipStream_t>(stream), nullptr);
 }
 
 extern "C" int fs_conv_wgrad(const FsWgradArgs* args, int dtype, void* stream) {
@@ -1500,22 +1430,11 @@ extern "C" int fs_conv_wgrad(const FsWgradArgs* args, int dtype, void* stream) {
 }
 
 extern "C" int fs_conv_wgrad_plan(const FsWgradArgs* args, int dtype, int32_t* plan) {
-  if (!args || !plan || args->M <= 0 || args->ncolgroups <= 0) return FS_EINVAL;
-  if (args->pro_a && (!args->pro_b || dtype != FS_DTYPE_BF16)) return FS_EINVAL;
-  g_plan = plan;
-  int r = FS_EINVAL;
-  if (dtype == FS_DTYPE_BF16) r = launch_wgrad<bf16>(*args, nullptr, nullptr);
-  else if (dtype == FS_DTYPE_F32) r = launch_wgrad<float>(*args, nullptr, nullptr);
-  g_plan = nullptr;
-  return r;
+  if (!plan || wgrad_check(args, dtype, false) != FS_OK) return FS_EINVAL;
+  return wgrad_run(args, nullptr, dtype, nullptr, plan);
 }
 
 extern "C" int fs_conv_wgrad2_plan(const FsWgradArgs* args, const FsWgradArgs* a1, int dtype, int32_t* plan) {
   if (!plan || wgrad_check(args, dtype) != FS_OK || (a1 && wgrad_check(a1, dtype) != FS_OK)) return FS_EINVAL;
-  g_plan = plan;
-  int r = FS_EINVAL;
-  if (dtype == FS_DTYPE_BF16) r = launch_wgrad<bf16>(*args, a1, nullptr);
-  else if (dtype == FS_DTYPE_F32) r = launch_wgrad<float>(*args, a1, nullptr);
-  g_plan = nullptr;
-  return r;
+  return wgrad_run(args, a1, dtype, nullptr, plan);
 }

@@ -114,6 +114,39 @@ def test_conv_fwd_bwd(dev, case, dtype):
     assert (dw.cpu() - wr.grad).abs().max().item() <= tol_w * wscale
 
 
+@pytest.mark.parametrize("case,dtype", [
+    ((64, 64, 3, 2, 16, 32), torch.bfloat16),      # LDS-halo kernel
+    ((16, 16, 3, 2, 48, 64), torch.bfloat16),      # narrow kernel
+    ((128, 128, 3, 3, 12, 20), torch.bfloat16),    # generic tile kernel
+    ((128, 128, 3, 3, 12, 20), torch.float32),
+    ((64, 64, 1, 4, 40, 64), torch.bfloat16),      # LDS-DMA 1x1 kernel
+])
+def test_wgrad_without_workspace(dev, case, dtype):
+    """workspace == NULL through the C ABI: no split, every main kernel adds its tile straight into the OIHW gradient (its own
+    offset arithmetic, no reduce launch); same bound as test_conv_fwd_bwd"""
+    import ctypes as C
+    from fsnet_amd.hip.binding import lib
+    from fsnet_amd.hip.conv import ConvOp
+    Ci, Co, k, N, H, W = case
+    g = torch.Generator().manual_seed(77 + Ci + k)
+    x = torch.randn(N, Ci, H, W, generator=g)
+    w = (torch.randn(Co, Ci, k, k, generator=g) / (Ci * k * k) ** 0.5).requires_grad_(True)
+    gy = torch.randn(N, Co, H, W, generator=g)
+    if dtype == torch.bfloat16:
+        x, gy = x.bfloat16().float(), gy.bfloat16().float()
+    F.conv2d(x, w, None, stride=1, padding=k // 2).backward(gy)
+    op = ConvOp(Ci, Co, k, k, 1, k // 2, dtype, dev)
+    dw = torch.zeros(Co, Ci, k, k, device=dev)
+    gyd, xd = to_nhwc(gy.to(dev), op.Co_p, dtype), to_nhwc(x.to(dev), op.Ci_p, dtype)
+    sp = op.wgrad_spec(gyd, xd, dw)
+    sp.a.workspace, sp.a.workspace_elems = 0, 0
+    tol = 5e-5 if dtype == torch.float32 else 2e-3
+    for n in (1, 2):                                 # the second call accumulates
+        assert lib.fs_conv_wgrad(C.byref(sp.a), sp.code, None) == 0
+        torch.cuda.synchronize()
+        assert (dw.cpu() - n * w.grad).abs().max().item() <= n * tol * w.grad.abs().max().item()
+
+
 def test_conv_addend_relu_strided(dev):
     """epilogue addend + relu, strided (padded-buffer interior) source and destination."""
     from fsnet_amd.hip.conv import ConvOp

@@ -50,6 +50,7 @@ LANE_CASES = [
     (256, 512, 3, 2, 1, 12, 40, 2, 4, 2),
     (512, 512, 3, 1, 1, 6, 20, 3, 6, 2),       # layer 4: groups of 360 rows (one statistics group per blockIdx.z)
     (6, 64, 7, 2, 3, 64, 128, 2, 4, 2),        # the stems pair although their real input channels differ (3 / 6): see below
+    (64, 64, 1, 1, 0, 40, 64, 2, 1, 1),        # 5120 + 2560 pixels: the pair's weight gradient on the LDS-DMA 1x1 kernel (bf16)
 ]
 
 
@@ -128,6 +129,41 @@ def test_two_weight_launch_against_two_conv2d_calls(dev, case, dtype):
     torch.cuda.synchronize()
     for p, dw in zip(P, dws):
         assert (dw.cpu() - 2 * p["dw_ref"]).abs().max().item() <= 2 * (5e-5 if dtype == torch.float32 else 2e-3) * p["dw_ref"].abs().max().item()
+
+
+def _wgrad2(P, workspace=True):
+    """fs_conv_wgrad2 on two problems (C ABI) -> their two dW; workspace=False: both argument sets without one"""
+    import ctypes as C
+    from fsnet_amd.hip.binding import lib
+    dws = [torch.zeros_like(p["dw_ref"], device=p["x"].device) for p in P]
+    specs = [p["op"].wgrad_spec(p["gy"], p["x"], dw) for p, dw in zip(P, dws)]
+    if not workspace:
+        for sp in specs:
+            sp.a.workspace, sp.a.workspace_elems = 0, 0
+    assert lib.fs_conv_wgrad2(C.byref(specs[0].a), C.byref(specs[1].a), specs[0].code, None) == 0
+    torch.cuda.synchronize()
+    return dws
+
+
+def test_pair_that_does_not_agree_on_a_kernel_runs_as_two_launches(dev):
+    """64 -> 64 with 128 -> 128 (both 3x3 at 16x32, the LDS-halo kernel): different dW shapes, no shared launch — each dW is
+    its single-problem launch's, bit for bit"""
+    dtype = torch.bfloat16
+    P = [_problem(dev, dtype, 64, 64, 3, 1, 1, 2, 16, 32, 21), _problem(dev, dtype, 128, 128, 3, 1, 1, 2, 16, 32, 22)]
+    dws = _wgrad2(P)
+    for p, dw in zip(P, dws):
+        solo = p["op"].wgrad(p["gy"], p["x"], torch.zeros_like(dw))
+        torch.cuda.synchronize()
+        assert torch.equal(dw, solo)
+        assert (dw.cpu() - p["dw_ref"]).abs().max().item() <= 2e-3 * p["dw_ref"].abs().max().item()
+
+
+def test_pair_without_a_workspace_runs_as_two_unsplit_launches(dev):
+    """workspace == NULL: nothing is split and nothing is shared; both dW come from the main kernel's direct `dW +=`"""
+    dtype = torch.bfloat16
+    P = [_problem(dev, dtype, 64, 64, 3, 1, 1, 2, 16, 32, 23), _problem(dev, dtype, 64, 64, 3, 1, 1, 2, 16, 32, 24)]
+    for p, dw in zip(P, _wgrad2(P, workspace=False)):
+        assert (dw.cpu() - p["dw_ref"]).abs().max().item() <= 2e-3 * p["dw_ref"].abs().max().item()
 
 
 def test_pair_shares_one_launch(dev):
