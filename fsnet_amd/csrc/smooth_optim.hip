@@ -1,13 +1,14 @@
 // Edge-aware smoothness loss (fwd + bwd, all scales per launch), the final loss assembly, and the
-// fused gradient-norm / clip / Adam update over a flat parameter arena.
+// fused gradient-norm / clip / Adam, AdamW or SGD update over a flat parameter arena.
 // Replaces:
 //   get_smooth_loss + mean-normalised disparity        monodepth_utils.py:168-181, monodepth2_decoder.py:294-299
 //   F.adaptive_avg_pool2d(original_image_0, (h, w))     monodepth2_decoder.py:214-219
 //   loss bookkeeping (loss/s, smooth_loss/s, total)     monodepth2_decoder.py:292-304, 343
-//   clip_grad_norm_ + torch.optim.Adam.step             base_training_hooks.py:46-49, optimizers.py:7-8
+//   clip_grad_norm_ + torch.optim.{Adam,AdamW,SGD}.step base_training_hooks.py:46-49, optimizers.py:4-11
 #include "common.h"
 #include "fsnet_hip_internal.h"
 #include <algorithm>
+#include <vector>
 
 namespace {
 
@@ -218,32 +219,121 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
 
 __global__ void counter_incr_kernel(int* p) { if (threadIdx.x == 0 && blockIdx.x == 0) *p += 1; }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, long n, float lr,
-                                                   float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                   float max_norm, const double* __restrict__ sumsq,
-                                                   float grad_scale, const int* __restrict__ step_ptr,
-                                                   const float* __restrict__ lr_ptr) {
-  if (step_ptr) {   // device-resident step count / learning rate: the launch can be replayed from a hipGraph
-    const float st = (float)*step_ptr;
-    bc1 = 1.f - powf(b1, st);
-    bc2_sqrt = sqrtf(1.f - powf(b2, st));
+// ---- the update kernels: one launch over the arena, or over the runs of it that hold trainable parameters ----
+// What the three updates share sits in optim_kernel: the device-resident step count and learning rate (the launch is
+// hipGraph-replayable), the fused clip, the walk over the run table in 16-byte units.  An update is a struct with
+//   NS                  how many state arrays it streams beside the parameter and the gradient (0, 1 or 2)
+//   begin(lr, t)        per-thread scalars; t > 0: the step count read from device memory
+//   apply(p, g, a, b)   one element: gradient already scaled and clipped, a / b its state
+struct AdamUpdate {          // torch.optim.Adam (decoupled = 0: L2 decay folded into the gradient) / AdamW (= 1)
+  static constexpr int NS = 2;
+  float b1, b2, eps, wd, bc1, bc2_sqrt;
+  int decoupled;
+  float step, keep;
+  __device__ void begin(float lr, int t) {
+    if (t > 0) {
+      const float st = (float)t;
+      bc1 = 1.f - powf(b1, st);
+      bc2_sqrt = sqrtf(1.f - powf(b2, st));
+    }
+    step = lr / bc1;
+    keep = 1.f - lr * wd;
   }
+  __device__ void apply(float& p, float gi, float& m, float& v) const {
+    float pi = p;
+    if (wd != 0.f) {
+      if (decoupled) pi *= keep;
+      else gi += wd * pi;
+    }
+    float mi = b1 * m + (1.f - b1) * gi;
+    float vi = b2 * v + (1.f - b2) * gi * gi;
+    m = mi; v = vi;
+    p = pi - step * mi / (sqrtf(vi) / bc2_sqrt + eps);
+  }
+};
+
+template <int MOMENTUM> struct SgdUpdate {   // torch.optim.SGD; MOMENTUM = 0 streams no buffer at all
+  static constexpr int NS = MOMENTUM;
+  float momentum, dampening, wd;
+  int nesterov, first;
+  float lr;
+  __device__ void begin(float lr_, int t) {
+    lr = lr_;
+    if (t > 0) first = t == 1;      // torch's first step stores the gradient as the buffer, undamped
+  }
+  __device__ void apply(float& p, float gi, float& buf, float&) const {
+    const float pi = p;
+    if (wd != 0.f) gi += wd * pi;
+    if (MOMENTUM) {
+      const float bi = first ? gi : momentum * buf + (1.f - dampening) * gi;
+      buf = bi;
+      gi = nesterov ? gi + momentum * bi : bi;
+    }
+    p = pi - lr * gi;
+  }
+};
+
+template <class U> __device__ __forceinline__ void update4(const U& u, float* __restrict__ p,
+                                                           const float* __restrict__ g, float* __restrict__ s0,
+                                                           float* __restrict__ s1, long i, float coef) {
+  float4 pv = *reinterpret_cast<const float4*>(p + i);
+  const float4 gv = *reinterpret_cast<const float4*>(g + i);
+  float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+  if (U::NS > 0) a = *reinterpret_cast<const float4*>(s0 + i);
+  if (U::NS > 1) b = *reinterpret_cast<const float4*>(s1 + i);
+  u.apply(pv.x, gv.x * coef, a.x, b.x);
+  u.apply(pv.y, gv.y * coef, a.y, b.y);
+  u.apply(pv.z, gv.z * coef, a.z, b.z);
+  u.apply(pv.w, gv.w * coef, a.w, b.w);
+  if (U::NS > 0) *reinterpret_cast<float4*>(s0 + i) = a;
+  if (U::NS > 1) *reinterpret_cast<float4*>(s1 + i) = b;
+  *reinterpret_cast<float4*>(p + i) = pv;
+}
+
+template <class U> __device__ __forceinline__ void update1(const U& u, float* __restrict__ p,
+                                                           const float* __restrict__ g, float* __restrict__ s0,
+                                                           float* __restrict__ s1, long i, float coef) {
+  float pi = p[i], a = 0.f, b = 0.f;
+  if (U::NS > 0) a = s0[i];
+  if (U::NS > 1) b = s1[i];
+  u.apply(pi, g[i] * coef, a, b);
+  if (U::NS > 0) s0[i] = a;
+  if (U::NS > 1) s1[i] = b;
+  p[i] = pi;
+}
+
+// runs: n_runs [lo, hi) element ranges (NULL: the one range [0, n)).  Nothing outside a run is read or written.  A run
+// is walked in 16-byte units between its first and last 16-byte boundary and element-wise outside them (vec = 0, a
+// base pointer off that alignment: element-wise throughout).  Run r starts at block r of the grid, so that a table of
+// many short runs spreads over the blocks instead of queueing on the first one.  A run that does not lie inside [0, n)
+// is skipped: the entry points reject such a table, but inside a stream capture they cannot read it.
+template <class U> __global__ __launch_bounds__(256) void optim_kernel(
+    U u, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1, long n,
+    const int64_t* __restrict__ runs, int n_runs, int vec, float lr, float max_norm, const double* __restrict__ sumsq,
+    float grad_scale, const int* __restrict__ step_ptr, const float* __restrict__ lr_ptr) {
   if (lr_ptr) lr = *lr_ptr;
+  u.begin(lr, step_ptr ? *step_ptr : 0);
   float coef = grad_scale;
   if (sumsq && max_norm > 0.f) {
     float norm = (float)sqrt(*sumsq) * grad_scale;
     coef *= fminf(max_norm / (norm + 1e-6f), 1.f);
   }
-  const float step = lr / bc1;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    float gi = g[i] * coef;
-    float pi = p[i];
-    if (wd != 0.f) gi += wd * pi;
-    float mi = b1 * m[i] + (1.f - b1) * gi;
-    float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    p[i] = pi - step * mi / (sqrtf(vi) / bc2_sqrt + eps);
+  const long G = gridDim.x;
+  const int R = runs ? n_runs : 1;
+  for (int r = 0; r < R; ++r) {
+    const long lo = runs ? (long)runs[2 * r] : 0, hi = runs ? (long)runs[2 * r + 1] : n;
+    if (lo < 0 || hi > n || hi <= lo) continue;
+    long a = hi, b = hi;                 // [lo, a) and [b, hi): element-wise; [a, b): 16-byte units
+    if (vec) {
+      a = (lo + 3) & ~3L;
+      if (a > hi) a = hi;
+      b = hi & ~3L;
+      if (b < a) b = a;
+    }
+    const long t = ((blockIdx.x + G - r % G) % G) * 256 + threadIdx.x;
+    for (long i = a + t * 4; i < b; i += G * 256 * 4) update4(u, p, g, s0, s1, i, coef);
+    for (long i = lo + t; i < a; i += G * 256) update1(u, p, g, s0, s1, i, coef);
+    for (long i = b + t; i < hi; i += G * 256) update1(u, p, g, s0, s1, i, coef);
   }
 }
 
@@ -337,15 +427,68 @@ extern "C" int fs_counter_incr(int* counter, void* stream) {
   return fs_launch_status();
 }
 
+// Reads a run table back to check it (blocking: the table is a few dozen bytes and the caller's stream is idle or about
+// to be); a stream that is being captured cannot be waited on, there the kernel's own range check stands alone.
+static bool runs_valid(const int64_t* runs, int n_runs, int64_t n, hipStream_t st) {
+  if (!runs) return n_runs == 0;
+  if (n_runs < 1 || n_runs > FS_MAX_RUNS) return false;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) != hipSuccess) return false;
+  if (cap != hipStreamCaptureStatusNone) return true;
+  std::vector<int64_t> host(2 * (size_t)n_runs);
+  if (hipMemcpyAsync(host.data(), runs, host.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return false;
+  for (int r = 0; r < n_runs; ++r)
+    if (host[2 * r] < 0 || host[2 * r + 1] < host[2 * r] || host[2 * r + 1] > n) return false;
+  return true;
+}
+
+template <class U> static int launch_optim(const U& u, float* p, const float* g, float* s0, float* s1, int64_t n,
+                                           float lr, float max_norm, const double* sumsq, float grad_scale,
+                                           const int* step_ptr, const float* lr_ptr, const int64_t* runs, int n_runs,
+                                           hipStream_t st) {
+  if (!runs_valid(runs, n_runs, n, st)) return FS_EINVAL;
+  const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)s0 | (uintptr_t)s1) & 15) == 0;
+  long blocks = std::min<long>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(optim_kernel<U>, dim3((unsigned)blocks), dim3(256), 0, st, u, p, g, s0, s1, (long)n, runs, n_runs,
+                     vec, lr, max_norm, sumsq, grad_scale, step_ptr, lr_ptr);
+  return fs_launch_status();
+}
+
+extern "C" int fs_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                             float beta2, float eps, float weight_decay, int decoupled, int step, float max_norm,
+                             const double* sumsq, float grad_scale, const int* step_ptr, const float* lr_ptr,
+                             const int64_t* runs, int n_runs, void* stream) {
+  if (!p || !g || !m || !v || n <= 0 || (step < 1 && !step_ptr)) return FS_EINVAL;
+  if (step < 1) step = 1;
+  AdamUpdate u;
+  u.b1 = beta1; u.b2 = beta2; u.eps = eps; u.wd = weight_decay; u.decoupled = decoupled != 0;
+  u.bc1 = 1.f - (float)pow((double)beta1, (double)step);
+  u.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  return launch_optim(u, p, g, m, v, n, lr, max_norm, sumsq, grad_scale, step_ptr, lr_ptr, runs, n_runs,
+                      reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int fs_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                             float beta2, float eps, float weight_decay, int step, float max_norm, const double* sumsq,
                             float grad_scale, const int* step_ptr, const float* lr_ptr, void* stream) {
-  if (!p || !g || !m || !v || n <= 0 || (step < 1 && !step_ptr)) return FS_EINVAL;
-  if (step < 1) step = 1;
-  float bc1 = 1.f - (float)pow((double)beta1, (double)step);
-  float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-  long blocks = std::min<long>((n + 255) / 256, 4096);
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, m, v,
-                     (long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, max_norm, sumsq, grad_scale, step_ptr, lr_ptr);
-  return fs_launch_status();
+  return fs_adamw_step(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, 0, step, max_norm, sumsq, grad_scale,
+                       step_ptr, lr_ptr, nullptr, 0, stream);
+}
+
+extern "C" int fs_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float dampening,
+                           int nesterov, float weight_decay, int step, float max_norm, const double* sumsq,
+                           float grad_scale, const int* step_ptr, const float* lr_ptr, const int64_t* runs, int n_runs,
+                           void* stream) {
+  if (!p || !g || n <= 0 || (momentum != 0.f && !buf) || (step < 1 && !step_ptr)) return FS_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (momentum == 0.f) {
+    SgdUpdate<0> u;
+    u.momentum = 0.f; u.dampening = dampening; u.wd = weight_decay; u.nesterov = 0; u.first = 0;
+    return launch_optim(u, p, g, nullptr, nullptr, n, lr, max_norm, sumsq, grad_scale, step_ptr, lr_ptr, runs, n_runs, st);
+  }
+  SgdUpdate<1> u;
+  u.momentum = momentum; u.dampening = dampening; u.wd = weight_decay; u.nesterov = nesterov != 0; u.first = step <= 1;
+  return launch_optim(u, p, g, buf, nullptr, n, lr, max_norm, sumsq, grad_scale, step_ptr, lr_ptr, runs, n_runs, st);
 }

@@ -15,9 +15,9 @@ fsnet_amd meta-archs and transparent for every other module:
   * DistributedDataParallel(module, ...)          -> for an fsnet_amd meta-arch, a thin wrapper with the same
     `.module` attribute / `module.`-prefixed state_dict / forward signature and no reducer
 
-plus `adopt_optimizer`: the reference's build_optimizer returns torch.optim.Adam (optimizers.py:7-8); the training
-hook adopts such an instance into the fused clip+Adam kernel, sharing its param_groups (schedulers keep working) and
-its state dict (checkpoints keep torch.optim.Adam's format).
+plus `adopt_optimizer`: the reference's build_optimizer returns torch.optim.SGD / Adam / AdamW (optimizers.py:4-11); the
+training hook adopts such an instance into the fused clip+update kernel, sharing its param_groups (schedulers keep
+working) and its state dict (checkpoints keep torch.optim's format).
 """
 import torch
 import torch.nn as nn
@@ -71,10 +71,14 @@ def install():
 
 
 def adopt_optimizer(optimizer, meta_arch):
-    """torch.optim.Adam over exactly the meta-arch's parameters -> FusedAdam sharing its param_groups and state;
-    anything else is returned unchanged (the hook then runs it as a plain torch optimizer)."""
-    from fsnet_amd.vision_base.networks.optimizers.optimizers import FusedAdam
-    if isinstance(optimizer, FusedAdam) or type(optimizer) is not torch.optim.Adam:
+    """torch.optim.Adam / AdamW / SGD over exactly the meta-arch's parameters -> FusedAdam / FusedAdamW / FusedSGD
+    sharing its param_groups and state; anything else is returned unchanged (the hook then runs it as a plain torch
+    optimizer)."""
+    from fsnet_amd.vision_base.networks.optimizers.optimizers import ArenaOptimizer, FusedAdam, FusedAdamW, FusedSGD
+    if isinstance(optimizer, ArenaOptimizer):
+        return optimizer
+    cls = {torch.optim.Adam: FusedAdam, torch.optim.AdamW: FusedAdamW, torch.optim.SGD: FusedSGD}.get(type(optimizer))
+    if cls is None:
         return optimizer
     fused = getattr(optimizer, "_fsnet_fused", None)
     if fused is not None:
@@ -82,12 +86,15 @@ def adopt_optimizer(optimizer, meta_arch):
     if len(optimizer.param_groups) != 1:
         return optimizer
     g = optimizer.param_groups[0]
-    if g.get("amsgrad") or g.get("maximize") or g.get("capturable") or g.get("differentiable"):
+    if any(g.get(k) for k in cls.UNSUPPORTED):
         return optimizer
     inner = getattr(meta_arch, "module", meta_arch)
     if [id(p) for p in g["params"]] != [id(p) for p in inner.parameters()]:
         return optimizer
-    fused = FusedAdam(g["params"], lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], model=inner)
+    if cls is FusedAdam:
+        fused = FusedAdam(g["params"], lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], model=inner)
+    else:
+        fused = cls(g["params"], lr=g["lr"], model=inner)     # (every other setting comes with the shared param_groups)
     fused.param_groups = optimizer.param_groups      # one list: a scheduler stepping the torch optimizer moves both
     fused.state = optimizer.state                    # one dict: checkpoints written from either see the moments
     optimizer.state_dict = fused.state_dict          # (refreshes the per-parameter step counts first)

@@ -655,6 +655,33 @@ def adam_step(p, g, m, v, lr, b1, b2, eps, wd, step, max_norm=0.0, sumsq_buf=Non
                            float(grad_scale), _p(step_buf), _p(lr_buf), stream_ptr()), "adam_step")
 
 
+def _runs(runs):
+    """run table (device int64 [R][2], or None: the whole span) -> (pointer, count)"""
+    if runs is None:
+        return None, 0
+    assert runs.dtype == torch.int64 and runs.is_contiguous() and runs.dim() == 2 and runs.shape[1] == 2
+    return runs.data_ptr(), runs.shape[0]
+
+
+def adamw_step(p, g, m, v, lr, b1, b2, eps, wd, step, decoupled=True, max_norm=0.0, sumsq_buf=None, grad_scale=1.0,
+               step_buf=None, lr_buf=None, runs=None):
+    """decoupled: torch.optim.AdamW's decay (False: Adam's L2 form, as adam_step); runs: only these [lo, hi) ranges"""
+    rp, rn = _runs(runs)
+    check(lib.fs_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(b1),
+                            float(b2), float(eps), float(wd), int(bool(decoupled)), int(step), float(max_norm or 0.0),
+                            _p(sumsq_buf), float(grad_scale), _p(step_buf), _p(lr_buf), rp, rn, stream_ptr()),
+          "adamw_step")
+
+
+def sgd_step(p, g, buf, lr, momentum, dampening, nesterov, wd, step, max_norm=0.0, sumsq_buf=None, grad_scale=1.0,
+             step_buf=None, lr_buf=None, runs=None):
+    """torch.optim.SGD; buf: the momentum buffer (None with momentum == 0); step == 1 stores the gradient as the buffer"""
+    rp, rn = _runs(runs)
+    check(lib.fs_sgd_step(p.data_ptr(), g.data_ptr(), _p(buf), p.numel(), float(lr), float(momentum), float(dampening),
+                          int(bool(nesterov)), float(wd), int(step), float(max_norm or 0.0), _p(sumsq_buf),
+                          float(grad_scale), _p(step_buf), _p(lr_buf), rp, rn, stream_ptr()), "sgd_step")
+
+
 COPY_MAX = 16
 
 

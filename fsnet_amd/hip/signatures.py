@@ -110,6 +110,9 @@ SIGNATURES = {
     "fs_sumsq": (C.c_int, [P, L, P, P, P]),
     "fs_counter_incr": (C.c_int, [P, P]),
     "fs_adam_step": (C.c_int, [P, P, P, P, L, F, F, F, F, F, I, F, P, F, P, P, P]),
+    # added under ABI 15: the update launch with a run table (runs, n_runs before the stream) — AdamW / Adam-L2, SGD
+    "fs_adamw_step": (C.c_int, [P, P, P, P, L, F, F, F, F, F, I, I, F, P, F, P, P, P, I, P]),
+    "fs_sgd_step": (C.c_int, [P, P, P, L, F, F, F, I, F, I, F, P, F, P, P, P, I, P]),
 }
 
 

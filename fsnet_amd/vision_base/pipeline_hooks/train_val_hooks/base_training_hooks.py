@@ -1,12 +1,13 @@
 """One optimisation step, with the reference hook's constructor and call signature
 (vision_base/pipeline_hooks/train_val_hooks/base_training_hooks.py:9-49): zero_grad -> H2D -> forward ->
-loss.backward() -> clip_grad_norm_ -> optimizer.step().  With the HIP FusedAdam the zero/clip/step
-collapse to one memset + two kernels over the flat arena, with no host synchronisation in the step.
+loss.backward() -> clip_grad_norm_ -> optimizer.step().  With the HIP arena optimizers (FusedAdam, FusedAdamW,
+FusedSGD) the zero/clip/step collapse to one memset + two kernels over the flat arena, with no host synchronisation in
+the step.
 
 hipGraph replay: the step launches several hundred small kernels on two streams and the host needs 8-10 ms to issue them,
 about what the GPU needs to run them.  After `graph_warmup` eager steps the hook captures the whole step
-(zero-grad memset, weight re-pack, both forward/backward chains, clip + Adam) into one hipGraph on a private
-stream and replays it; the per-step scalars (Adam step count, learning rate, tie-break noise seed) live in
+(zero-grad memset, weight re-pack, both forward/backward chains, clip + update) into one hipGraph on a private
+stream and replays it; the per-step scalars (optimizer step count, learning rate, tie-break noise seed) live in
 device memory, so a replay is a real step.  Inputs are copied into static device buffers; the returned
 tensors are the graph's static outputs, valid until the next call (loss_dict entries are cloned when a logger
 is attached).  Eager execution stays in use for non-fused optimizers, whenever the batch signature changes, and for
@@ -155,12 +156,15 @@ class BaseTrainingHook(object):
         return output
 
     # ------------------------------------------------------------------ graph path
-    def _signature(self, data, meta_arch, optimizer):
+    def _signature(self, data, meta_arch, optimizer, arena):
         sig = [id(meta_arch), id(optimizer), self.clip_gradients]
-        # Adam's betas / eps / weight decay are baked into the captured launch (only lr and the step count live in
-        # device memory): changing them re-captures
+        # the update's constants (Adam's betas / eps, SGD's momentum / dampening / nesterov, the weight decay) and the run
+        # table of trainable parameters are baked into the captured launch (only lr and the step count live in device
+        # memory): changing them, or freezing / unfreezing a parameter, re-captures
         for g in getattr(optimizer, "param_groups", []):
-            sig.append((tuple(g.get("betas", ())), g.get("eps"), g.get("weight_decay")))
+            sig.append((tuple(g.get("betas", ())), g.get("eps"), g.get("weight_decay"), g.get("momentum"),
+                        g.get("dampening"), g.get("nesterov")))
+        sig.append(optimizer.run_mask(arena))
         for k, v in data.items():
             if isinstance(v, torch.Tensor):
                 sig.append((k, tuple(v.shape), v.dtype))
@@ -303,11 +307,11 @@ class BaseTrainingHook(object):
     def __call__(self, data, meta_arch, optimizer, writer=None, training_loss_logger=None, global_step=0,
                  epoch_num=0):
         from fsnet_amd.engine.torch_compat import adopt_optimizer
-        from fsnet_amd.vision_base.networks.optimizers.optimizers import FusedAdam
+        from fsnet_amd.vision_base.networks.optimizers.optimizers import ArenaOptimizer
         inner = getattr(meta_arch, "module", meta_arch)
-        optimizer = adopt_optimizer(optimizer, meta_arch)     # torch.optim.Adam from the reference's build_optimizer
+        optimizer = adopt_optimizer(optimizer, meta_arch)     # torch.optim.* from the reference's build_optimizer
         arena = inner.ensure_arena() if hasattr(inner, "ensure_arena") else None
-        fused = isinstance(optimizer, FusedAdam)
+        fused = isinstance(optimizer, ArenaOptimizer)
         meta = dict(epoch_num=epoch_num, global_step=global_step, is_training=True)
         logger = training_loss_logger
 
@@ -320,7 +324,7 @@ class BaseTrainingHook(object):
                 return self._tune_eager_step(data, meta_arch, optimizer, arena, fused, meta, logger)
             return self._eager_step(data, meta_arch, optimizer, arena, fused, meta, logger)
 
-        sig = self._signature(data, meta_arch, optimizer)
+        sig = self._signature(data, meta_arch, optimizer, arena)
         if sig != self._g_sig or (self._g is not None and not self._g["arena"] is arena):
             # (the old signature's graph stays parked, see _PARKED: it is not replayed again — objects the model caches per
             # batch geometry, the loss chain's buffers among them, are rebuilt for the new one and the old graph's pointers

@@ -823,6 +823,24 @@ int fs_counter_incr(int32_t* counter, void* stream);
 int fs_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                  float eps, float weight_decay, int step, float max_norm, const double* sumsq, float grad_scale,
                  const int32_t* step_ptr, const float* lr_ptr, void* stream);
+/* Added under ABI 15: the same launch with a run table, for AdamW and SGD as well.
+ * runs / n_runs: device array of n_runs [lo, hi) element ranges of the arena (int64 pairs, at most FS_MAX_RUNS); only
+ * elements inside a run are read or written — parameter, gradient and state alike.  NULL / 0: the one range [0, n).
+ * A table with lo < 0, hi < lo or hi > n returns FS_EINVAL and launches nothing; the entry reads it back for that (a
+ * blocking copy of n_runs * 16 bytes), except on a stream that is being captured, where the kernel skips such a run.
+ * fs_adamw_step: decoupled = 1 is torch.optim.AdamW (p *= 1 - lr * wd, gradient untouched), decoupled = 0 is
+ * fs_adam_step's L2 form.
+ * fs_sgd_step: torch.optim.SGD (momentum, dampening, nesterov, L2 weight decay).  The first step stores the gradient as
+ * the momentum buffer, undamped: `step` (or *step_ptr, which overrides it) == 1 selects that.  momentum == 0: buf may be
+ * NULL, no buffer is read or written. */
+#define FS_MAX_RUNS 4096
+int fs_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                  float eps, float weight_decay, int decoupled, int step, float max_norm, const double* sumsq,
+                  float grad_scale, const int32_t* step_ptr, const float* lr_ptr, const int64_t* runs, int n_runs,
+                  void* stream);
+int fs_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float dampening,
+                int nesterov, float weight_decay, int step, float max_norm, const double* sumsq, float grad_scale,
+                const int32_t* step_ptr, const float* lr_ptr, const int64_t* runs, int n_runs, void* stream);
 
 #ifdef __cplusplus
 }
