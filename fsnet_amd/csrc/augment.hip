@@ -9,6 +9,9 @@
 //   ConvertToTensor (HWC -> CHW)                                                                        :62-88
 // The random draws and the O(B) bookkeeping (P2, relative poses) stay on the host in the mirrored classes
 // (fsnet_amd/vision_base/data/augmentations); this kernel receives them as a per-sample plan.
+// A patched_mask that is not all ones (NusceneJsonDataset's CAM_BACK) rides in the same launch through the *_masked
+// entry points: mask_src, a uint8 0/1 plane in the frames' padded extent, is read at the INTER_NEAREST coordinate
+// (nearest.h) and written as f64; without a plane the mask of ones is synthesised from the coordinate alone.
 // cv2 is a third-party dependency absent from the reference tree: warpAffine follows OpenCV's imgwarp.cpp (matrix
 // inverted in f64 by the host, 10-bit fixed-point coordinates, 1/32-pixel bilinear grid, BORDER_CONSTANT 0) and
 // cvtColor its color_hsv RGB2HSV_f / HSV2RGB_f (hrange 360) — see oracle/augment_oracle.py ("parity unpinned").
@@ -16,11 +19,12 @@
 // IEEE), so the result equals the numpy restatement bit for bit.
 #include "common.h"
 #include "fsnet_hip_internal.h"
+#include "nearest.h"
 #include <cstdint>
 
 namespace {
 
-constexpr int AB_BITS = 10, INTER_BITS = 5, INTER_TAB = 1 << INTER_BITS;
+constexpr int AB_BITS = FS_WARP_AB_BITS, INTER_BITS = 5, INTER_TAB = 1 << INTER_BITS;
 constexpr float FLT_EPS = 1.1920929e-07f;
 
 __device__ __forceinline__ void rgb2hsv(float r, float g, float b, float& h, float& s, float& v) {
@@ -73,7 +77,7 @@ __device__ __forceinline__ void colour_chain(float (&c)[3], const int32_t* ip, c
   }
 }
 
-__global__ __launch_bounds__(256) void augment_frames_kernel(const FsAugArgs p) {
+__global__ __launch_bounds__(256) void augment_frames_kernel(const FsAugArgs p, const uint8_t* mask_src) {
   const int b = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= p.H * p.W) return;
@@ -84,19 +88,19 @@ __global__ __launch_bounds__(256) void augment_frames_kernel(const FsAugArgs p) 
   const int sh = ip[5], sw = ip[6];
   const int x = ip[4] ? p.W - 1 - xo : xo;                 // RandomMirror: out[:, xo] = warped[:, W-1-xo]
 
-  // cv2.warpAffine coordinates: saturate_cast<int>(double) = round-half-even
-  const long adelta = (long)rint(m[0] * (double)x * (double)(1 << AB_BITS));
-  const long bdelta = (long)rint(m[3] * (double)x * (double)(1 << AB_BITS));
-  const long X00 = (long)rint((m[1] * (double)y + m[2]) * (double)(1 << AB_BITS));
-  const long Y00 = (long)rint((m[4] * (double)y + m[5]) * (double)(1 << AB_BITS));
+  const FsWarpFixed c0 = fs_warp_fixed(m, x, y);           // cv2.warpAffine coordinates
 
-  {   // patched_mask: ones warped with INTER_NEAREST -> 1 where the nearest source pixel exists
-    const long rd = (1 << AB_BITS) / 2;
-    const long sx = (X00 + rd + adelta) >> AB_BITS, sy = (Y00 + rd + bdelta) >> AB_BITS;
-    if (p.mask) p.mask[((long)b * p.H + y) * p.W + xo] = (sx >= 0 && sx < sw && sy >= 0 && sy < sh) ? 1.0 : 0.0;
+  if (p.mask) {   // patched_mask warped with INTER_NEAREST: the mask's value (1 without a plane) where the nearest
+                  // source pixel exists, BORDER_CONSTANT 0 elsewhere
+    long nx, ny;
+    double v = 0.0;
+    if (!mask_src) v = fs_warp_nearest(c0, sh, sw, nx, ny) ? 1.0 : 0.0;
+    else if (fs_warp_nearest(c0, min(sh, p.Hs), min(sw, p.Ws), nx, ny))   // a plan past the plane reads nothing
+      v = (double)mask_src[((long)b * p.Hs + ny) * p.Ws + nx];
+    p.mask[((long)b * p.H + y) * p.W + xo] = v;
   }
   const long rd = (1 << AB_BITS) / INTER_TAB / 2;
-  const long X = (X00 + rd + adelta) >> (AB_BITS - INTER_BITS), Y = (Y00 + rd + bdelta) >> (AB_BITS - INTER_BITS);
+  const long X = (c0.X + rd) >> (AB_BITS - INTER_BITS), Y = (c0.Y + rd) >> (AB_BITS - INTER_BITS);
   const long sx = X >> INTER_BITS, sy = Y >> INTER_BITS;
   const float fx = (float)(X & (INTER_TAB - 1)) / (float)INTER_TAB, fy = (float)(Y & (INTER_TAB - 1)) / (float)INTER_TAB;
   const float w00 = (1.f - fy) * (1.f - fx), w01 = (1.f - fy) * fx, w10 = fy * (1.f - fx), w11 = fy * fx;
@@ -143,7 +147,7 @@ __device__ __forceinline__ void resize_coord(int d, double scale, int n, int& s0
   s0 = sx; f = fx;
 }
 
-__global__ __launch_bounds__(256) void resize_frames_kernel(const FsResizeArgs p) {
+__global__ __launch_bounds__(256) void resize_frames_kernel(const FsResizeArgs p, const uint8_t* mask_src) {
   const int b = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= p.H * p.W) return;
@@ -161,8 +165,16 @@ __global__ __launch_bounds__(256) void resize_frames_kernel(const FsResizeArgs p
   }
   const int x1 = min(x0 + 1, sw - 1), y1 = min(y0 + 1, sh - 1);
   const long HW = (long)p.H * p.W;
-  // patched_mask: ones through cv2.resize(INTER_NEAREST) are ones; the padding is zero
-  if (p.mask) p.mask[((long)b * p.H + y) * p.W + xo] = inside ? 1.0 : 0.0;
+  // patched_mask through cv2.resize(INTER_NEAREST): the plane's value (ones without a plane); the padding is zero
+  if (p.mask) {
+    double v = inside ? 1.0 : 0.0;
+    if (inside && mask_src) {
+      const int ny = min(max(fs_resize_nearest(y, rh, sh), 0), p.Hs - 1);   // inside the plane whatever dims say
+      const int nx = min(max(fs_resize_nearest(x, rw, sw), 0), p.Ws - 1);
+      v = (double)mask_src[((long)b * p.Hs + ny) * p.Ws + nx];
+    }
+    p.mask[((long)b * p.H + y) * p.W + xo] = v;
+  }
   for (int f = 0; f < p.F; ++f) {
     const uint8_t* src = p.src + ((long)b * p.F + f) * p.Hs * p.Ws * 3;
     const long o = (((long)f * p.B + b) * 3) * HW + (long)y * p.W + xo;
@@ -188,25 +200,40 @@ __global__ __launch_bounds__(256) void resize_frames_kernel(const FsResizeArgs p
   }
 }
 
-}  // namespace
-
-extern "C" int fs_resize_frames(const FsResizeArgs* a, void* stream) {
+int launch_resize(const FsResizeArgs* a, const uint8_t* mask_src, void* stream) {
   if (!a || !a->src || !a->dims || !a->image) return FS_EINVAL;
   if ((a->iplan != nullptr) != (a->fplan != nullptr)) return FS_EINVAL;
   if (a->B < 1 || a->F < 1 || a->H < 1 || a->W < 1 || a->Hs < 1 || a->Ws < 1) return FS_EINVAL;
   if ((long)a->Hs * a->Ws * 3 > 0x7fffffffL) return FS_EINVAL;
   for (int k = 0; k < 3; ++k) if (a->std[k] == 0.f) return FS_EINVAL;
   dim3 grid((unsigned)(((long)a->H * a->W + 255) / 256), (unsigned)a->B);
-  hipLaunchKernelGGL(resize_frames_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a);
+  hipLaunchKernelGGL(resize_frames_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a, mask_src);
   return fs_launch_status();
 }
 
-extern "C" int fs_augment_frames(const FsAugArgs* a, void* stream) {
+int launch_augment(const FsAugArgs* a, const uint8_t* mask_src, void* stream) {
   if (!a || !a->src || !a->minv || !a->iplan || !a->fplan || (!a->image && !a->original)) return FS_EINVAL;
   if (a->B < 1 || a->F < 1 || a->H < 1 || a->W < 1 || a->Hs < 1 || a->Ws < 1) return FS_EINVAL;
   if ((long)a->Hs * a->Ws * 3 > 0x7fffffffL) return FS_EINVAL;
   for (int k = 0; k < 3; ++k) if (a->std[k] == 0.f) return FS_EINVAL;
   dim3 grid((unsigned)(((long)a->H * a->W + 255) / 256), (unsigned)a->B);
-  hipLaunchKernelGGL(augment_frames_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a);
+  hipLaunchKernelGGL(augment_frames_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a, mask_src);
   return fs_launch_status();
+}
+
+}  // namespace
+
+extern "C" int fs_resize_frames(const FsResizeArgs* a, void* stream) { return launch_resize(a, nullptr, stream); }
+
+extern "C" int fs_augment_frames(const FsAugArgs* a, void* stream) { return launch_augment(a, nullptr, stream); }
+
+// the same launches with the batch's patched masks: a plane needs somewhere to go
+extern "C" int fs_resize_frames_masked(const FsResizeArgs* a, const uint8_t* mask_src, void* stream) {
+  if (!a || !mask_src || !a->mask) return FS_EINVAL;
+  return launch_resize(a, mask_src, stream);
+}
+
+extern "C" int fs_augment_frames_masked(const FsAugArgs* a, const uint8_t* mask_src, void* stream) {
+  if (!a || !mask_src || !a->mask) return FS_EINVAL;
+  return launch_augment(a, mask_src, stream);
 }

@@ -18,6 +18,7 @@
 // No atomics, every sum in a fixed order: the result is bit-identical from run to run and across batchings.
 #include "common.h"
 #include "fsnet_hip_internal.h"
+#include "nearest.h"
 #include <cmath>
 
 namespace {
@@ -318,24 +319,14 @@ __global__ __launch_bounds__(256) void of_augment_masks(const uint8_t* src, cons
   const uint8_t* s = src + (long)b * Hs * Ws;
   float v = 0.f;
   if (minv) {
-    constexpr int AB = 10;
-    const double* m = minv + b * 6;
     const int sh = iplan[b * FS_AUG_IPLAN + 5], sw = iplan[b * FS_AUG_IPLAN + 6];
-    const long adelta = (long)rint(m[0] * (double)x * (double)(1 << AB));
-    const long bdelta = (long)rint(m[3] * (double)x * (double)(1 << AB));
-    const long X00 = (long)rint((m[1] * (double)y + m[2]) * (double)(1 << AB));
-    const long Y00 = (long)rint((m[4] * (double)y + m[5]) * (double)(1 << AB));
-    const long rd = (1 << AB) / 2;
-    const long sx = (X00 + rd + adelta) >> AB, sy = (Y00 + rd + bdelta) >> AB;
-    if (sx >= 0 && sx < sw && sy >= 0 && sy < sh) v = (float)s[sy * Ws + sx];
+    long sx, sy;
+    if (fs_warp_nearest(fs_warp_fixed(minv + b * 6, x, y), sh, sw, sx, sy)) v = (float)s[sy * Ws + sx];
   } else {
     const int32_t* d = dims + b * 4;
     const int sh = d[0], sw = d[1], rh = d[2], rw = d[3];
-    if (y < rh && x < rw) {
-      const int sx = min((int)floor((double)x * (1.0 / ((double)rw / (double)sw))), sw - 1);
-      const int sy = min((int)floor((double)y * (1.0 / ((double)rh / (double)sh))), sh - 1);
-      v = (float)s[(long)sy * Ws + sx];
-    }
+    if (y < rh && x < rw)
+      v = (float)s[(long)fs_resize_nearest(y, rh, sh) * Ws + fs_resize_nearest(x, rw, sw)];
   }
   out[(long)b * H * W + i] = v;
 }

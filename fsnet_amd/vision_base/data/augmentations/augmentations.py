@@ -32,8 +32,9 @@ def _plan(data):
 
 
 def _extra_gt(data, keys, shape):
-    """ground-truth images other than the synthesised patched_mask (e.g. a precomputed 'motion_mask'): uint8 [H, W] of
-    the frame's size, kept raw for DeviceAugment, which samples them with the frames' plan (fs_augment_masks)"""
+    """ground-truth images other than the patched_mask, which rides in the frames' launch (e.g. a precomputed
+    'motion_mask'): uint8 [H, W] of the frame's size, kept raw for DeviceAugment, which samples them with the frames'
+    plan (fs_augment_masks)"""
     plan = _plan(data)
     extra = plan.setdefault("gt_extra", [])
     for key in keys:
@@ -45,6 +46,25 @@ def _extra_gt(data, keys, shape):
                 key, getattr(m, "dtype", type(m)), getattr(m, "shape", "")))
         if key not in extra:
             extra.append(key)
+
+
+def _patched_mask(data, keys, shape):
+    """the sample's patched_mask when `keys` (a stage's gt_image_keys) lists it: every pixel is looked at.  All ones is
+    the mask the kernels synthesise and leaves the plan alone; values in {0, 1} (NusceneJsonDataset zeroes the car's own
+    body in CAM_BACK, nuscene_dataset.py:176-191) are recorded as uint8 for DeviceAugment, which samples them in the
+    frames' launch (fs_augment_frames_masked / fs_resize_frames_masked).  The sample's own entry stays as the dataset
+    made it."""
+    if 'patched_mask' not in keys or 'patched_mask' not in data:
+        return
+    m = np.asarray(data['patched_mask'])
+    if m.shape[:2] != tuple(shape[:2]):
+        raise NotImplementedError("the device path samples a patched_mask of the frame's size %s, got %s" % (
+            tuple(shape[:2]), m.shape))
+    if bool(np.all(m == 1)):
+        return
+    if m.ndim != 2 or not bool(np.all((m == 0) | (m == 1))):
+        raise NotImplementedError("the device path samples a [H, W] patched_mask with values in {0, 1}")
+    _plan(data)["patched_mask"] = m.astype(np.uint8)
 
 
 def _frame_shape(data, key):
@@ -105,11 +125,7 @@ class Resize(object):
         if plan["warp"] is not None or plan.get("resize") is not None or plan["ops"] or plan["mirror"]:
             raise NotImplementedError("Resize is the first (and only geometric) stage of a device pipeline")
         _extra_gt(data, self.gt_image_keys, shape)
-        for key in self.gt_image_keys:
-            if key == 'patched_mask' and key in data:
-                m = np.asarray(data[key])
-                if m.shape[:2] != tuple(shape[:2]) or not bool(np.all(m[::8, ::8] == 1)):
-                    raise NotImplementedError("the device path resizes an all-ones patched_mask of the frame's size")
+        _patched_mask(data, self.gt_image_keys, shape)
         data[('image_resize', 'original_shape')] = np.array([shape[0], shape[1]]).astype(int)
         if self.preserve_aspect_ratio:
             scale_factor_x = self.size[0] / shape[0]
@@ -159,6 +175,7 @@ class RandomWarpAffine(object):
         center_w = self.rng.integers(low=self.shift_border, high=width - self.shift_border)
         center_h = self.rng.integers(low=self.shift_border, high=height - self.shift_border)
         _extra_gt(data, self.gt_image_keys, (height, width))
+        _patched_mask(data, self.gt_image_keys, (height, width))
         final_scale = max(self.output_w, self.output_h) / scale
         shift_w = self.output_w / 2 - center_w * final_scale
         shift_h = self.output_h / 2 - center_h * final_scale
@@ -442,9 +459,26 @@ class DeviceAugment(object):
         batch = {PLAN: dict(src=src, dims=torch.from_numpy(dims), iplan=torch.from_numpy(iplan),
                             fplan=torch.from_numpy(fplan), mean=mean, std=std, out_hw=(r0["out_h"], r0["out_w"]),
                             kind="resize", train=True, mask='patched_mask' in r0.get("gt_keys", []))}
+        if not batch[PLAN]["mask"] and any(p.get("patched_mask") is not None for p in plans):
+            raise ValueError("samples of one batch must carry the same ground-truth images")
+        self._collate_mask(plans, batch, Hs, Ws, "resize")
         self._collate_gt(samples, plans, batch)
         self._collate_rest(samples, batch)
         return batch
+
+    @staticmethod
+    def _collate_mask(plans, batch, Hs, Ws, stage):
+        """the patched masks that are not all ones (_patched_mask): one uint8 [B, Hs, Ws] plane in the frames' padded
+        extent, ones for the samples that recorded none.  Nearest indices are clamped to a sample's own extent, so the
+        zero padding is never read.  A batch without such a sample carries no plane and uploads nothing extra."""
+        if all(p.get("patched_mask") is None for p in plans):
+            return
+        t = torch.zeros(len(plans), Hs, Ws, dtype=torch.uint8)
+        for b, p in enumerate(plans):
+            h, w = p[stage]["src_hw"]
+            m = p.get("patched_mask")
+            t.numpy()[b, :h, :w] = 1 if m is None else m
+        batch[PLAN]["mask_src"] = t
 
     @staticmethod
     def _collate_gt(samples, plans, batch):
@@ -520,6 +554,7 @@ class DeviceAugment(object):
             iplan[b, 5], iplan[b, 6] = h, w
         batch = {PLAN: dict(src=src, minv=torch.from_numpy(minv), iplan=torch.from_numpy(iplan),
                             fplan=torch.from_numpy(fplan), mean=mean, std=std, out_hw=(out_h, out_w), kind="warp")}
+        self._collate_mask(plans, batch, Hs, Ws, "warp")
         self._collate_gt(samples, plans, batch)
         self._collate_rest(samples, batch)
         return batch
@@ -532,6 +567,7 @@ class DeviceAugment(object):
         src = plan["src"].to(device, non_blocking=True)
         B, F, Hs, Ws, _ = src.shape
         H, W = plan["out_hw"]
+        mask_src = plan["mask_src"].to(device, non_blocking=True) if plan.get("mask_src") is not None else None
         if plan["kind"] == "resize":
             dims = plan["dims"].to(device, non_blocking=True)
             image = torch.empty(F, B, 3, H, W, dtype=torch.float32, device=device)
@@ -549,7 +585,10 @@ class DeviceAugment(object):
                 if plan.get("mask"):
                     mask = torch.empty(B, H, W, dtype=torch.float64, device=device)
                     r.mask = mask.data_ptr()
-            check(lib.fs_resize_frames(C.byref(r), stream_ptr()), "resize_frames")
+            if mask_src is not None:
+                check(lib.fs_resize_frames_masked(C.byref(r), mask_src.data_ptr(), stream_ptr()), "resize_masked")
+            else:
+                check(lib.fs_resize_frames(C.byref(r), stream_ptr()), "resize_frames")
             for f, idx in enumerate(self.frame_idxs):
                 batch[(self.image_family, idx)] = image[f]
                 if original is not None:
@@ -573,7 +612,10 @@ class DeviceAugment(object):
         for k in range(3):
             a.mean[k], a.std[k] = float(plan["mean"][k]), float(plan["std"][k])
         a.B, a.F, a.Hs, a.Ws, a.H, a.W = B, F, Hs, Ws, H, W
-        check(lib.fs_augment_frames(C.byref(a), stream_ptr()), "augment_frames")
+        if mask_src is not None:
+            check(lib.fs_augment_frames_masked(C.byref(a), mask_src.data_ptr(), stream_ptr()), "augment_masked")
+        else:
+            check(lib.fs_augment_frames(C.byref(a), stream_ptr()), "augment_frames")
         for f, idx in enumerate(self.frame_idxs):
             batch[(self.image_family, idx)] = image[f]
             batch[(self.original_family, idx)] = original[f]

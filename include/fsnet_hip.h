@@ -334,6 +334,18 @@ typedef struct FsResizeArgs {
 } FsResizeArgs;
 int fs_resize_frames(const FsResizeArgs* args, void* stream);
 
+/* The two launches above with a patched_mask that is not all ones (NusceneJsonDataset's CAM_BACK zeroes the car's own
+ * body, nuscene_dataset.py:176-191; gt images through Resize / RandomWarpAffine, augmentations.py:163-164, :436-497).
+ * Added entry points, the argument structs are unchanged: FS_ABI_VERSION stays.  mask_src: the batch's masks, uint8 0/1
+ * [B][Hs][Ws] in the padded extent of args->src (sample b's mask in the top-left src_h x src_w), sampled with
+ * INTER_NEAREST by the launch that samples the frames, mirrored with them and written to args->mask as f64.
+ * Warp: the value at the nearest fixed-point coordinate, 0 where it leaves the sample's src_h x src_w.  Resize: inside
+ * the resized rh x rw area the value at min(floor(d * (n_src / n_dst)), n_src - 1), scale in f64; the padding stays 0.
+ * The mask index is kept inside the plane whatever the per-sample extents say.  Everything else is the unmasked
+ * launch bit for bit.  FS_EINVAL when mask_src or args->mask is NULL. */
+int fs_augment_frames_masked(const FsAugArgs* args, const uint8_t* mask_src, void* stream);
+int fs_resize_frames_masked(const FsResizeArgs* args, const uint8_t* mask_src, void* stream);
+
 /* Evaluation.  fs_resize_linear: single-channel fp32 [h][w] -> [H][W] with OpenCV's INTER_LINEAR
  * rule; invert != 0 resizes the inverse: dst = 1 / resize(1 / src)  (base_evaluation_hooks.py:57).
  * fs_depth_eval: per image b, pred [B][h][w] (resized on the fly to the ground truth's [H][W]) against gt [B][H][W]:

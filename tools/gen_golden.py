@@ -511,6 +511,41 @@ def gen_augment_resize():
     np.savez_compressed(os.path.join(GOLD, "augment_resize.npz"), **res)
 
 
+def gen_augment_mask():
+    """A patched_mask that is not all ones (NusceneJsonDataset's CAM_BACK, nuscene_dataset.py:176-191) through the REAL
+    reference Resize, RandomWarpAffine and RandomMirror, built by the reference's own builder over the cases of
+    tests/helpers_patched_mask.py, each with the mirror drawn on and off.  cv2.resize / cv2.warpAffine are the shim's
+    restatement (unpinned, as in gen_augment_resize); what this pins is the reference's own handling of the mask: the
+    order nearest resample -> pad / crop -> mirror, the modes, the dtype."""
+    from tests import helpers_patched_mask as HM
+    if not hasattr(np, "int"):
+        np.int = int
+    res = dict(resize_size=np.array(HM.RESIZE_SIZE), warp_out=np.array([HM.WARP_OUT_H, HM.WARP_OUT_W]))
+    maxdev = 0.0
+    for mirror in (False, True):
+        transform = build(**HM.geometry_cfg("resize", mirror))
+        for n, (frames, mask) in enumerate(HM.resize_inputs()):
+            out = transform(HM.sample_dict(frames, mask))
+            got = np.asarray(out['patched_mask'])
+            assert got.dtype == np.float64 and set(np.unique(got)) <= {0.0, 1.0}
+            res["resize%d_m%d" % (n, mirror)] = got.astype(np.uint8)
+            res["resize%d_effective" % n] = np.asarray(out[('image_resize', 'effective_size')])
+            maxdev = max(maxdev, float(np.abs(HM.expect_resize(mask, mirror) - got).max()))
+        transform = build(**HM.geometry_cfg("warp", mirror))          # a fresh instance: the same seeded draws
+        inputs = HM.warp_inputs()
+        Ms = HM.warp_matrices([m.shape for _, m in inputs])
+        for n, (frames, mask) in enumerate(inputs):
+            out = transform(HM.sample_dict(frames, mask))
+            got = np.asarray(out['patched_mask'])
+            assert got.dtype == np.float64 and set(np.unique(got)) <= {0.0, 1.0}
+            res["warp%d_m%d" % (n, mirror)] = got.astype(np.uint8)
+            res["warp%d_M" % n] = Ms[n]
+            maxdev = max(maxdev, float(np.abs(HM.expect_warp(mask, Ms[n], mirror) - got).max()))
+    res["dtype"] = np.array("float64")
+    print("augment-mask: oracle composition vs reference classes, max abs deviation %.3e" % maxdev)
+    np.savez_compressed(os.path.join(GOLD, "augment_mask.npz"), **res)
+
+
 def gen_fisheye():
     """Fisheye path (BASELINE configs[3]) through the REAL classes: MeiCameraProjection LUT + cam2image
     (mei_fisheye_utils.py:14-187) and FishEyeDecoder.loss with gradients (monodepth2_decoder.py:350-420)."""
@@ -1496,6 +1531,9 @@ if __name__ == "__main__":
     if "--only-augment-resize" in sys.argv:
         gen_augment_resize()
         sys.exit(0)
+    if "--only-augment-mask" in sys.argv:
+        gen_augment_mask()
+        sys.exit(0)
     if "--only-fisheye" in sys.argv:
         gen_fisheye()
         sys.exit(0)
@@ -1544,6 +1582,7 @@ if __name__ == "__main__":
     gen_frozen()
     gen_concat()
     gen_augment_resize()
+    gen_augment_mask()
     gen_no_overlap_mask()
     gen_velo_gt()
     gen_postopt()
