@@ -10,16 +10,11 @@
 // lane's MFMA operand (8 consecutive channels of one pixel) is ONE 16-byte global load — and all pixel loads of a
 // K chunk are in flight while the weights are staged.  MFMA roles as in conv_igemm (A = weights, B = pixels), so the
 // epilogue (bias, addend, ReLU, ReLU-backward mask, BatchNorm statistics / backward sums, fp32 output, statistics
-// groups) is the same code.
+// groups) is the same as conv_igemm.hip's: its value lines are repeated here, the statistics tail is conv_epi.h's.
 #include <cstdlib>
-#include "common.h"
-#include "fsnet_hip_internal.h"
+#include "conv_epi.h"
 
 namespace {
-
-__device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0));
-}
 
 // KC: channels of the K walk staged per chunk (64 / 128 / 256); CO: channel tile; the four waves split the 128-pixel
 // tile (32 pixels = two MFMA column tiles each) and every wave multiplies the whole channel tile.
@@ -45,16 +40,9 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(const FsConvArgs p, const 
   const int li = lane & 15, lg = lane >> 4;
   const int n0 = p.grp_imgs > 0 ? (int)blockIdx.z * p.grp_imgs : 0;
 
-  // XCD-aware tile mapping (see conv_igemm.hip): pixel tiles of one channel tile share an XCD's L2 copy of its weights
+  // XCD-aware tile mapping (conv_epi.h): pixel tiles of one channel tile share an XCD's L2 copy of its weights
   int px, cy;
-  {
-    const int npix = (p.M + PIX - 1) / PIX, nco = p.Co_p / CO;
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    if (nco % 8 == 0) { const int g = nco >> 3; cy = xcd + 8 * (slot % g); px = slot / g; }
-    else if (8 % nco == 0) { const int g = 8 / nco; cy = xcd % nco; px = slot * g + xcd / nco; }
-    else { cy = id % nco; px = id / nco; }
-    if (px >= npix) return;
-  }
+  if (!conv_xcd_tile(blockIdx.x, p.Co_p / CO, (p.M + PIX - 1) / PIX, 0, px, cy)) return;
   const int pix0 = px * PIX, co0 = cy * CO;
   const int OOB = 0x7fffffff;
   const __amdgpu_buffer_rsrc_t rs_src =
@@ -93,14 +81,14 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(const FsConvArgs p, const 
 #pragma unroll
       for (int b = 0; b < TP; ++b) {
         const int ko = kb + kk * 64;
-        fb[kk][b] = buf_load16(rs_src, (pvoff[b] == OOB || ko + lg * 16 >= kbytes) ? OOB : pvoff[b] + ko);
+        fb[kk][b] = conv_load16(rs_src, (pvoff[b] == OOB || ko + lg * 16 >= kbytes) ? OOB : pvoff[b] + ko);
       }
     uint4 rc[LCU];
 #pragma unroll
     for (int i = 0; i < LCU; ++i) {
       const int idx = t + i * 256;
       const int row = idx / UR, u = idx - row * UR;
-      rc[i] = buf_load16(rs_wgt, (row < CO && kb + u * 16 < kbytes) ? (co0 + row) * wrow_bytes + kb + u * 16 : OOB);
+      rc[i] = conv_load16(rs_wgt, (row < CO && kb + u * 16 < kbytes) ? (co0 + row) * wrow_bytes + kb + u * 16 : OOB);
     }
     if (kc > 0) __syncthreads();               // previous chunk's weights fully multiplied
 #pragma unroll
@@ -128,13 +116,16 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(const FsConvArgs p, const 
   }
 
   // ---- epilogue: lane holds, for pixel (tile b, li), channels lg*4..lg*4+3 of channel tile a ----
+  // (the 4-channel value pipeline in this kernel's own lines, the same as conv_igemm.hip's; conv_epi.h states the
+  // statistics tail — DESIGN section 24)
   float s1[TC][4], s2[TC][4];
 #pragma unroll
   for (int a = 0; a < TC; ++a)
 #pragma unroll
     for (int j = 0; j < 4; ++j) { s1[a][j] = 0.f; s2[a][j] = 0.f; }
-  const long sgoff = p.grp_imgs > 0 ? (long)blockIdx.z * p.Co
-                                    : (p.stat_group_rows > 0 ? (long)(pix0 / p.stat_group_rows) * p.Co : 0);
+  // statistics group of this tile (groups are multiples of the tile height: fs_conv1x1 checks)
+  const long sg = p.grp_imgs > 0 ? (long)blockIdx.z : (p.stat_group_rows > 0 ? (long)(pix0 / p.stat_group_rows) : 0);
+  const long sgoff = sg * p.Co;
 
 #pragma unroll
   for (int b = 0; b < TP; ++b) {
@@ -211,46 +202,18 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(const FsConvArgs p, const 
   }
 
   if (p.stats) {
-    // per-channel (sum, sumsq): 16 pixel lanes by shuffle, the WP pixel-waves through LDS, then ONE f64
-    // atomic per channel per block into one of FS_STAT_SLOTS address slots (same-address atomics cost
-    // ~12 ns each on MI355X; slots + block reduce keep the chain per address short).
     __syncthreads();                     // all waves are done reading the operand tiles
     float* red = reinterpret_cast<float*>(&lds_c[0]);   // [WP][CO][2]
-#pragma unroll
-    for (int a = 0; a < TC; ++a)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float u = s1[a][j], w = s2[a][j];
-        u = row16_sum(u); w = row16_sum(w);     // over the 16 pixel lanes of this channel (DPP, no LDS)
-        if (li == 0) {
-          int cl = wc * WCO + a * 16 + lg * 4 + j;
-          red[(wp * CO + cl) * 2] = u; red[(wp * CO + cl) * 2 + 1] = w;
-        }
-      }
+    epi_row_sums<TC>(s1, s2, red + wp * CO * 2, wc * WCO, li, lg);
     __syncthreads();
-    if (t < CO) {
-      float u = 0.f, w = 0.f;
-#pragma unroll
-      for (int k = 0; k < WP; ++k) { u += red[(k * CO + t) * 2]; w += red[(k * CO + t) * 2 + 1]; }
-      int co = co0 + t;
-      if (co < p.Co) {
-        // statistics group of this tile (groups are multiples of the tile height: fs_conv_igemm checks)
-        const long sg = p.grp_imgs > 0 ? (long)blockIdx.z : (p.stat_group_rows > 0 ? pix0 / p.stat_group_rows : 0);
-        double* sl = p.stats + (sg * FS_STAT_SLOTS + px % FS_STAT_SLOTS) * 2 * p.Co;
-        atomicAdd(sl + co, (double)u);
-        atomicAdd(sl + p.Co + co, (double)w);
-      }
-    }
+    epi_stats_tail<CO, WP>(red, t, co0, p.Co, p.stats, sg, px);
   }
 }
-
 
 template <typename T, int CO, int KC>
 int launch_1x1(const FsConvArgs& a, hipStream_t st) {
   constexpr int PIX = 128;
-  const int npix = (a.M + PIX - 1) / PIX, nco = a.Co_p / CO;
-  int blocks = npix * nco;
-  if (nco % 8 != 0 && 8 % nco == 0) { const int g = 8 / nco; blocks = 8 * ((npix + g - 1) / g); }
+  const int blocks = conv_xcd_blocks((a.M + PIX - 1) / PIX, a.Co_p / CO, 0);
   hipLaunchKernelGGL((conv1x1_kernel<T, CO, KC>), dim3(blocks, 1, a.grp_imgs > 0 ? a.N / a.grp_imgs : 1), dim3(256), 0, st,
                      a, fs_make_div(a.Wd), fs_make_div(a.Hd));
   return fs_launch_status();
@@ -266,7 +229,8 @@ int launch_co(const FsConvArgs& a, hipStream_t st) {
 }  // namespace
 
 // FS_EINVAL = "not a case for this kernel" (the caller falls back to fs_conv_igemm): fp32, a padded / dilated walk, a
-// parity-class data gradient, a K extent that is not whole 64-byte steps.
+// parity-class data gradient, a K extent that is not whole 64-byte steps, the derived ReLU mask (bnb_scale: the 3x3
+// kernels' option — no 1x1 kernel applies it, so none may accept it).
 extern "C" int fs_conv1x1(const FsConvArgs* args, int dtype, void* stream) {
   if (!args || !args->src || !args->wgt || !args->dst) return FS_EINVAL;
   if (dtype != FS_DTYPE_BF16 || args->dshift != 0 || args->ncls > 1 || args->hb_add != 0 || args->hb_mul < 1) return FS_EINVAL;
@@ -274,6 +238,7 @@ extern "C" int fs_conv1x1(const FsConvArgs* args, int dtype, void* stream) {
   if (args->src_bytes <= 0 || args->src_bytes > 0x7fffffffLL || args->wgt_bytes <= 0 || args->wgt_bytes > 0x7fffffffLL)
     return FS_EINVAL;
   if (args->stats && args->stat_group_rows > 0 && args->stat_group_rows % 128 != 0) return FS_EINVAL;
+  if (args->bnb_scale) return FS_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   {
     // LDS-DMA GEMM kernel first; what it declines (< 128 rows, channel counts that are not multiples of 8) streams rows

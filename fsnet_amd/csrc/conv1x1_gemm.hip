@@ -18,12 +18,11 @@
 //     (EPI: forward / data gradient / general), the data gradient's requesting the next row's operands a row ahead;
 //   * a block walks several pixel tiles where BatchNorm sums are carried and adds them with one round of f64 atomics;
 //   * channel tiles of one pixel tile run back to back on one XCD, so the pixel rows come from HBM once.
-// Epilogue semantics are conv1x1.hip's / conv_igemm.hip's (bias, addend, ReLU, mask, BatchNorm statistics or
+// Epilogue semantics are conv_epi.h's (bias, addend, ReLU, mask, BatchNorm statistics or
 // backward sums with statistics groups, fp32 output).  Measurements: DESIGN section 18.
 #include <algorithm>
 #include <cstdlib>
-#include "common.h"
-#include "fsnet_hip_internal.h"
+#include "conv_epi.h"
 #include "lds_dma.h"
 
 namespace {
@@ -337,14 +336,15 @@ __global__ __launch_bounds__(256, NST == 2 && PIX == 128 ? (EPI == 1 ? 3 : 4) : 
   }   // pixel tiles of the block
 
   if (p.stats) {
-    // ONE f64 atomic per channel and block into one of FS_STAT_SLOTS address slots (as conv1x1.hip)
+    // ONE f64 atomic per channel and block into one of FS_STAT_SLOTS address slots (conv_epi.h; the waves' sums are
+    // paired (a + b) + (c + d) here, not added in wave order as epi_stats_tail does)
     const int pix0 = spx * pt * PIX;
     __syncthreads();
     if (t < CO) {
       const int c = co0 + t;
       if (c < p.Co) {
         const long sg = p.grp_imgs > 0 ? (long)blockIdx.z : (p.stat_group_rows > 0 ? pix0 / p.stat_group_rows : 0);
-        double* sl = p.stats + (sg * FS_STAT_SLOTS + spx % FS_STAT_SLOTS) * 2 * p.Co;
+        double* sl = epi_stat_slot(p.stats, sg, spx, p.Co);
         const float* sw = reinterpret_cast<const float*>(lds + G::WORK);
         atomicAdd(sl + c, (double)((sw[2 * t] + sw[CO * 2 + 2 * t]) + (sw[CO * 4 + 2 * t] + sw[CO * 6 + 2 * t])));
         atomicAdd(sl + p.Co + c, (double)((sw[2 * t + 1] + sw[CO * 2 + 2 * t + 1]) + (sw[CO * 4 + 2 * t + 1] + sw[CO * 6 + 2 * t + 1])));

@@ -14,33 +14,17 @@
 // Arithmetic intensity: 98 FLOP per fetched byte on a 128x64 tile, 67 on 128x32 (2-3x the generic kernel) — but see
 // dispatch(): occupancy, not reuse, decides the tile on the monodepth shapes.
 // Dgrad = same kernel on dY with Wt[ci][r][s][co] and the taps mirrored (sgn = -1).
-// The epilogue (bias / addend / ReLU / ReLU-mask / fp32 out / fused BN statistics) matches conv_igemm.hip.
+// The epilogue (bias / addend / ReLU / ReLU-mask / fp32 out / fused BN statistics) follows conv_epi.h.
 // Round 4: the operand prologue of conv3x3_t32.hip (conv_pro.h: BatchNorm + ReLU in front of the convolution, coefficients
 // derived in the kernel) and the derived ReLU mask (bnb_scale) exist here too, so that every BasicBlock of every stage folds, not only the launches large
 // enough for the 32x32-tile kernel.
-#include "common.h"
-#include "fsnet_hip_internal.h"
+#include "conv_epi.h"
 #include "conv_pro.h"
-#include <algorithm>
 #include <cstdlib>
 
 namespace {
 
 __device__ __forceinline__ int swz64(int row) { return ((row >> 3) & 1) << 1; }
-
-__device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0));
-}
-
-// workgroup barrier that orders LDS traffic only.  __syncthreads() also carries a workgroup-scope fence, which on
-// gfx9 is `s_waitcnt vmcnt(0)`: every barrier then waits for the block's outstanding global loads AND stores (one
-// L2 round trip per barrier — PMC on the layer-1 shapes: waves parked 58 % of their cycles).  LDS hand-offs between
-// the waves of a block only need the DS counter drained.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 struct HaloGeom {
   int TH, TW;        // pixel tile
@@ -99,7 +83,7 @@ __global__ __launch_bounds__(256, halo_minwaves(PIX, CO, PRO)) void conv3x3_halo
   const int nhalo = HH * HW;
   const int ntile = g.TH * g.TW;
 
-  // ---- tile mapping: XCD-aware over the channel tiles (see conv_igemm.hip) ----
+  // ---- tile mapping: conv_epi.h's conv_xcd_tile, spelled out (what this kernel keeps) ----
   const int npix = p.N * g.tiles_y * g.tiles_x, nco = p.Co_p / CO;
   int px, cy;
   {
@@ -159,9 +143,9 @@ __global__ __launch_bounds__(256, halo_minwaves(PIX, CO, PRO)) void conv3x3_halo
   auto load_regs = [&](int cc) {
     const int coff = cc * 64;
 #pragma unroll
-    for (int i = 0; i < LH; ++i) rh[i] = buf_load16(rs_src, hvoff[i] == OOB ? OOB : hvoff[i] + coff);
+    for (int i = 0; i < LH; ++i) rh[i] = conv_load16(rs_src, hvoff[i] == OOB ? OOB : hvoff[i] + coff);
 #pragma unroll
-    for (int i = 0; i < LW; ++i) rw[i] = buf_load16(rs_wgt, wvoff[i] == OOB ? OOB : wvoff[i] + coff);
+    for (int i = 0; i < LW; ++i) rw[i] = conv_load16(rs_wgt, wvoff[i] == OOB ? OOB : wvoff[i] + coff);
   };
   auto store_lds = [&](int cc) {
     float ka[PRO != 0 ? UN : 1], kb[PRO != 0 ? UN : 1];
@@ -228,9 +212,9 @@ __global__ __launch_bounds__(256, halo_minwaves(PIX, CO, PRO)) void conv3x3_halo
   const int nchunk = (p.Cs * (int)sizeof(T) + 63) / 64;
   load_regs(0);
   for (int cc = 0; cc < nchunk; ++cc) {
-    lds_barrier();                 // previous chunk fully multiplied (first pass: the coefficient table is complete)
+    conv_lds_barrier();                 // previous chunk fully multiplied (first pass: the coefficient table is complete)
     store_lds(cc);
-    lds_barrier();
+    conv_lds_barrier();
     if (cc + 1 < nchunk) load_regs(cc + 1);
     // (the compiler's own schedule of this tap walk — every fragment read next to its use — is as fast as a hand-
     // pipelined one with the reads one or two taps ahead: measured)
@@ -265,7 +249,8 @@ __global__ __launch_bounds__(256, halo_minwaves(PIX, CO, PRO)) void conv3x3_halo
     }
   }
 
-  // ---- epilogue ----
+  // ---- epilogue: the 4-channel value pipeline in this kernel's own lines, channel-only operands hoisted per channel tile
+  // (what this kernel keeps and why); the statistics tail is conv_epi.h's ----
   // (the data-gradient options do not exist in the stride-2 forward variant: their arguments are then never loaded)
   const bool has_add = STR == 1 && p.addend != nullptr, has_mask = STR == 1 && p.mask != nullptr;
   const bool has_bnb = STR == 1 && p.bnb_x != nullptr, has_mbn = has_bnb && p.bnb_scale != nullptr;
@@ -341,56 +326,19 @@ __global__ __launch_bounds__(256, halo_minwaves(PIX, CO, PRO)) void conv3x3_halo
     }
   }
   if (p.stats) {
-    lds_barrier();
+    const int sg = p.stat_group_rows > 0 ? fs_div(n, g.dIPG) : 0;   // whole images
+    conv_lds_barrier();
     float* red = reinterpret_cast<float*>(&lds_w[0]);   // [WP][CO][2]
-#pragma unroll
-    for (int a = 0; a < TC; ++a)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float u = s1[a][j], w = s2[a][j];
-        u = row16_sum(u); w = row16_sum(w);     // over the 16 pixel lanes of this channel (DPP, no LDS)
-        if (li == 0) {
-          int cl = wc * WCO + a * 16 + lg * 4 + j;
-          red[(wp * CO + cl) * 2] = u; red[(wp * CO + cl) * 2 + 1] = w;
-        }
-      }
-    lds_barrier();
-    if (t < CO) {
-      float u = 0.f, w = 0.f;
-#pragma unroll
-      for (int k = 0; k < WP; ++k) { u += red[(k * CO + t) * 2]; w += red[(k * CO + t) * 2 + 1]; }
-      int co = co0 + t;
-      if (co < p.Co) {
-        const long sg = p.stat_group_rows > 0 ? fs_div(n, g.dIPG) : 0;   // whole images
-        double* sl = p.stats + (sg * FS_STAT_SLOTS + px % FS_STAT_SLOTS) * 2 * p.Co;
-        atomicAdd(sl + co, (double)u);
-        atomicAdd(sl + p.Co + co, (double)w);
-      }
-    }
+    epi_row_sums<TC>(s1, s2, red + wp * CO * 2, wc * WCO, li, lg);
+    conv_lds_barrier();
+    epi_stats_tail<CO, WP>(red, t, co0, p.Co, p.stats, sg, px);
   }
   // (last, so that its arguments are not live across the walk: saved statistics / running statistics / dgamma, dbeta)
   if constexpr (PRO != 0) { if (bid == 0) pro_block0<PRO>(p, t, 256); }
 }
 
-// pick the pixel tile (TH x TW <= PIX, halo <= hmax) that wastes the fewest lanes, preferring wide tiles
-HaloGeom pick_geom(int Hd, int Wd, int PIX, int hmax) {
-  HaloGeom best{0, 0, 0, 0, 0u, 0u, FsDiv{0u, 0u}, FsDiv{0u, 0u}, FsDiv{0u, 0u}, FsDiv{0u, 0u}, 0};
-  double best_cost = 1e30;
-  for (int tw = std::min(4, Wd); tw <= std::min(Wd, 64); ++tw) {
-    int th = std::min(PIX / tw, Hd);
-    if (th < 1 || (th + 2) * (tw + 2) > hmax) continue;
-    int tx = (Wd + tw - 1) / tw, ty = (Hd + th - 1) / th;
-    double waste = (double)tx * ty * PIX / ((double)Hd * Wd);          // MFMA lanes spent per useful pixel
-    double halo = (double)(th + 2) * (tw + 2) / ((double)th * tw);     // fetch overhead
-    double cost = waste * (1.0 + 0.15 * halo);
-    if (cost < best_cost - 1e-9) { best_cost = cost; best.TH = th; best.TW = tw; best.tiles_x = tx; best.tiles_y = ty; }
-  }
-  if (best.TW > 0) {
-    best.mTW = fs_div_magic(best.TW); best.mHW = fs_div_magic(best.TW + 2);
-    best.dTX = fs_make_div(best.tiles_x); best.dTY = fs_make_div(best.tiles_y);
-  }
-  return best;
-}
+// the stride-1 pixel tile (conv_epi.h): a 2-pixel halo border, no width preference
+HaloGeom pick_geom(int Hd, int Wd, int PIX, int hmax) { return conv_pick_tile<HaloGeom>(Hd, Wd, PIX, hmax, 2, false); }
 
 // stride 2: TH x TW output pixels whose (2TH+1) x (2TW+2) halo slots fit
 HaloGeom pick_geom_s2(int Hd, int Wd, int PIX, int hmax) {
@@ -417,20 +365,8 @@ HaloGeom pick_geom_s2(int Hd, int Wd, int PIX, int hmax) {
 template <int PIX, int CO, int STR>
 int halo_problem(const FsConvArgs& a, HaloGeom& g) {
   g = STR == 2 ? pick_geom_s2(a.Hd, a.Wd, PIX, halo_hmax(PIX, 2)) : pick_geom(a.Hd, a.Wd, PIX, halo_hmax(PIX, 1));
-  if (g.TH == 0) return 0;
-  if (a.stat_group_rows > 0) {
-    const long hw = (long)a.Hd * a.Wd;
-    if (a.stat_group_rows % hw != 0) return 0;                  // statistics groups are whole images
-    g.dIPG = fs_make_div((int)(a.stat_group_rows / hw));
-  }
   if (a.pro_group_imgs > 0) g.dPRG = fs_make_div(a.pro_group_imgs);
-  const int npix = a.N * g.tiles_x * g.tiles_y, nco = a.Co_p / CO;
-  int blocks = npix * nco;
-  // which operand is worth keeping XCD-local: the input activation (fetched once per channel tile) or the weights
-  g.pix_major = (nco > 1 && a.src_bytes > 2 * a.wgt_bytes) ? 1 : 0;
-  if (g.pix_major) blocks = 8 * ((npix + 7) / 8) * nco;
-  else if (nco % 8 != 0 && 8 % nco == 0) { const int q = 8 / nco; blocks = 8 * ((npix + q - 1) / q); }
-  return blocks;
+  return conv_tile_grid(a, g, CO);
 }
 
 // b != nullptr: a second problem of the same shape class (conv3x3_pairable) in the same launch

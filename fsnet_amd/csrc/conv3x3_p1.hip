@@ -5,25 +5,14 @@
 // 9-18 KB of weights and re-derived its tile indices for every 11 KB halo it multiplied, 5 760 blocks of them at 192x640.
 // Here the weights are staged ONCE per block and the block walks pixel tiles b, b + grid, ... with the next tile's halo in
 // flight while the current one is multiplied and stored (the same lesson as the BatchNorm passes, bn.hip: what every block
-// repeats must be small against what it moves).  Same arguments, packed weights and epilogue as conv3x3_halo.hip; no operand
+// repeats must be small against what it moves).  Same arguments, packed weights and epilogue semantics (conv_epi.h) as conv3x3_halo.hip; no operand
 // prologue.  Entered through fs_conv3x3_halo.
-#include "common.h"
-#include "fsnet_hip_internal.h"
-#include <algorithm>
+#include "conv_epi.h"
 #include <cstdlib>
 
 namespace {
 
 __device__ __forceinline__ int p1_swz64(int row) { return ((row >> 3) & 1) << 1; }
-__device__ __forceinline__ uint4 p1_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0));
-}
-__device__ __forceinline__ void p1_barrier() {       // LDS-only workgroup barrier (global loads stay in flight)
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 struct P1Geom {
   int TH, TW, tiles_x, tiles_y, ntiles;
   unsigned mTW, mHW;
@@ -63,7 +52,7 @@ __global__ __launch_bounds__(256, CO == 16 ? 3 : 2) void conv3x3_p1_kernel(const
       const int idx = t + i * 256, q = idx & 3, rt = idx >> 2;
       const int tap = rt / CO, row = rt - tap * CO;
       const int off = (tap < 9 && q * 16 < row_bytes) ? row * wrow_bytes + tap * row_bytes + q * 16 : OOB;
-      const uint4 w = p1_load16(rs_wgt, off);
+      const uint4 w = conv_load16(rs_wgt, off);
       if (rt < 9 * CO) lds_w[rt * 4 + (q ^ p1_swz64(rt))] = w;
     }
   }
@@ -110,7 +99,7 @@ __global__ __launch_bounds__(256, CO == 16 ? 3 : 2) void conv3x3_p1_kernel(const
     for (int i = 0; i < LH; ++i) {
       const int hy = hyx[i] >> 16, hx = hyx[i] & 0xffff;
       const bool ok = hyx[i] >= 0 && (unsigned)(oy + hy) < (unsigned)p.Hs && (unsigned)(ox + hx) < (unsigned)p.Ws;
-      rh[i] = p1_load16(rs_src, ok ? (int)(base + hrel[i]) : OOB);
+      rh[i] = conv_load16(rs_src, ok ? (int)(base + hrel[i]) : OOB);
     }
   };
 
@@ -134,7 +123,7 @@ __global__ __launch_bounds__(256, CO == 16 ? 3 : 2) void conv3x3_p1_kernel(const
   load_tile(blockIdx.x);
   store_halo();
   if ((int)blockIdx.x + gstep < g.ntiles) load_tile(blockIdx.x + gstep);
-  p1_barrier();                    // weights and the first halo are in LDS
+  conv_lds_barrier();                    // weights and the first halo are in LDS
   for (int tile = blockIdx.x; tile < g.ntiles; tile += gstep) {
     f32x4 acc[TC][TP];
 #pragma unroll
@@ -172,13 +161,14 @@ __global__ __launch_bounds__(256, CO == 16 ? 3 : 2) void conv3x3_p1_kernel(const
         }
     }
 
-    p1_barrier();                  // every wave has read its fragments: the halo buffer is free
+    conv_lds_barrier();                  // every wave has read its fragments: the halo buffer is free
     if (tile + gstep < g.ntiles) {
       store_halo();                                                     // (requested one multiplication phase ago)
       if (tile + 2 * gstep < g.ntiles) load_tile(tile + 2 * gstep);
     }
 
-    // ---- epilogue of this tile (conv3x3_halo.hip's, per tile) ----
+    // ---- epilogue of this tile: conv3x3_halo.hip's value pipeline and statistics tail in this kernel's own lines — through
+    // conv_epi.h's shared tail the tap loop of this persistent walk is re-scheduled ----
     int n, y0, x0;
     tile_origin(tile, n, y0, x0);
     const int sgoff = p.stat_group_rows > 0 ? fs_div(n, g.dIPG) * p.Co : 0;
@@ -248,17 +238,9 @@ __global__ __launch_bounds__(256, CO == 16 ? 3 : 2) void conv3x3_p1_kernel(const
       }
     }
     if (p.stats) {
-#pragma unroll
-      for (int a = 0; a < TC; ++a)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float u = row16_sum(s1[a][j]), w = row16_sum(s2[a][j]);     // over the 16 pixel lanes of this channel (DPP)
-          if (li == 0) {
-            const int cl = a * 16 + lg * 4 + j;
-            red[(wp * CO + cl) * 2] = u; red[(wp * CO + cl) * 2 + 1] = w;
-          }
-        }
-      p1_barrier();
+      epi_row_sums<TC>(s1, s2, red + wp * CO * 2, 0, li, lg);
+      conv_lds_barrier();
+      // (epi_stats_tail's steps, spelled out: see above)
       if (t < CO) {
         float u = 0.f, w = 0.f;
 #pragma unroll
@@ -271,50 +253,22 @@ __global__ __launch_bounds__(256, CO == 16 ? 3 : 2) void conv3x3_p1_kernel(const
         }
       }
     }
-    p1_barrier();                  // next halo complete in LDS; the statistics hand-off buffer is free again
+    conv_lds_barrier();                  // next halo complete in LDS; the statistics hand-off buffer is free again
   }
 }
 
-P1Geom p1_pick_geom(int Hd, int Wd) {
-  P1Geom best{};
-  double best_cost = 1e30;
-  for (int tw = std::min(4, Wd); tw <= std::min(Wd, 64); ++tw) {
-    const int th = std::min(256 / tw, Hd);
-    if (th < 1 || (th + 2) * (tw + 2) > 360) continue;
-    const int tx = (Wd + tw - 1) / tw, ty = (Hd + th - 1) / th;
-    const double waste = (double)tx * ty * 256 / ((double)Hd * Wd);
-    const double halo = (double)(th + 2) * (tw + 2) / ((double)th * tw);
-    const double cost = waste * (1.0 + 0.15 * halo);
-    if (cost < best_cost - 1e-9) { best_cost = cost; best.TH = th; best.TW = tw; best.tiles_x = tx; best.tiles_y = ty; }
-  }
-  if (best.TW > 0) {
-    best.mTW = fs_div_magic(best.TW); best.mHW = fs_div_magic(best.TW + 2);
-    best.dTX = fs_make_div(best.tiles_x); best.dTY = fs_make_div(best.tiles_y);
-  }
-  return best;
-}
-
+// blocks of `kernel` the chip holds at once
 template <typename K>
 int p1_resident(K kernel) {
-  int dev = 0, cus = 256, per_cu = 1;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    hipDeviceProp_t pr;
-    if (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount;
-  }
+  int per_cu = 1;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-  return cus * per_cu;
+  return conv_cu_count() * per_cu;
 }
 
 template <typename T, int CO, int UQ>
 int p1_launch(const FsConvArgs& a, hipStream_t st) {
-  P1Geom g = p1_pick_geom(a.Hd, a.Wd);
-  if (g.TH == 0) return FS_EINVAL;
-  g.dIPG = FsDiv{0u, 0u};
-  if (a.stat_group_rows > 0) {
-    const long hw = (long)a.Hd * a.Wd;
-    if (a.stat_group_rows % hw != 0) return FS_EINVAL;
-    g.dIPG = fs_make_div((int)(a.stat_group_rows / hw));
-  }
+  P1Geom g = conv_pick_tile<P1Geom>(a.Hd, a.Wd, 256, 360, 2, false);      // (conv3x3_halo.hip's 256-pixel tile)
+  if (g.TH == 0 || !conv_stat_group_div(a, g.dIPG)) return FS_EINVAL;
   const long ntiles = (long)a.N * g.tiles_x * g.tiles_y;
   // worth it from two tiles per resident block on (below that the one-tile-per-block kernel has as little to repeat)
   // (FsConvArgs.force_impl = 5: a test forces small launches onto this kernel)

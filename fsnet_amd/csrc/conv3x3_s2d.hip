@@ -69,16 +69,8 @@ __global__ __launch_bounds__(256, 3) void conv3x3_s2d_kernel(const FsDual<FsConv
   const int nhalo = (g.TH + 1) * HW;
   const int ntile = g.TH * g.TW;
 
-  const int npix = p.N * g.tiles_y * g.tiles_x, nco = p.Co_p / CO;
-  int px, cy;
-  {
-    const int id = bid, xcd = id & 7, slot = id >> 3;
-    if (g.pix_major) { cy = slot % nco; px = (slot / nco) * 8 + xcd; }
-    else if (nco % 8 == 0) { const int q = nco >> 3; cy = xcd + 8 * (slot % q); px = slot / q; }
-    else if (8 % nco == 0) { const int q = 8 / nco; cy = xcd % nco; px = slot * q + xcd / nco; }
-    else { cy = id % nco; px = id / nco; }
-    if (px >= npix) return;
-  }
+  int px, cy;     // XCD-aware tile mapping (conv_epi.h)
+  if (!conv_xcd_tile(bid, p.Co_p / CO, p.N * g.tiles_y * g.tiles_x, g.pix_major, px, cy)) return;
   const int tq = fs_div(px, g.dTX); const int tx_i = px - tq * g.tiles_x;
   const int n = fs_div(tq, g.dTY); const int ty_i = tq - n * g.tiles_y;
   const int y0 = ty_i * g.TH, x0 = tx_i * g.TW;
@@ -172,9 +164,9 @@ __global__ __launch_bounds__(256, 3) void conv3x3_s2d_kernel(const FsDual<FsConv
   const int nchunk = (row_bytes + 63) / 64;
   load_regs(0);
   for (int cc = 0; cc < nchunk; ++cc) {
-    t32_barrier();
+    conv_lds_barrier();
     store_lds();
-    t32_barrier();
+    conv_lds_barrier();
     if (cc + 1 < nchunk) load_regs(cc + 1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -194,12 +186,13 @@ __global__ __launch_bounds__(256, 3) void conv3x3_s2d_kernel(const FsDual<FsConv
     }
   }
 
-  // ---- epilogue (conv3x3_t32.hip: accumulators through the wave's LDS region, 8 channels of one pixel per lane) ----
-  const bool has_add = T32_FLAG(EP_ADDEND, p.addend != nullptr);
-  const bool has_mask = T32_FLAG(EP_MASK, p.mask != nullptr);
+  // ---- epilogue (conv3x3_t32.hip's: accumulators through the wave's LDS region, conv_epi.h's pipeline on 8 channels of
+  // one pixel per lane; no bias, ReLU, derived mask or output statistics on this path) ----
   const bool has_bnb = T32_FLAG(EP_BNB, p.bnb_x != nullptr);
+  const EpiOpt opt{false, T32_FLAG(EP_ADDEND, p.addend != nullptr), false, T32_FLAG(EP_MASK, p.mask != nullptr), has_bnb,
+                   false, false};
 
-  t32_barrier();
+  conv_lds_barrier();
   float* ep = reinterpret_cast<float*>(lds + wave * (32 * EPS));
   const int l15 = lane & 15, cs = lane >> 4;
   int doff[2];
@@ -214,6 +207,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_s2d_kernel(const FsDual<FsConv
   float* red = reinterpret_cast<float*>(lds + PIX * EPS);       // [4 waves][CO][2]
   const int co = co0 + cs * 8;
   const bool cok = co < p.Co;
+  const EpiCh<8> k{};
   float s1[8], s2[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
@@ -235,26 +229,11 @@ __global__ __launch_bounds__(256, 3) void conv3x3_s2d_kernel(const FsDual<FsConv
       const int y = doff[i] >> 16, x = doff[i] & 0xffff;
       const int dof = n * (int)p.dN + y * (int)p.dH + x * (int)p.dW + py * (int)(p.dH >> 1) + pxx * (int)(p.dW >> 1);
       float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-      if (has_add) {
-        float av[8];
-        load8<T>(reinterpret_cast<const T*>(p.addend) + n * (int)p.aN + y * (int)p.aH + x * (int)p.aW +
-                     py * (int)(p.aH >> 1) + pxx * (int)(p.aW >> 1) + co, av);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] += av[j];
-      }
-      if (has_mask) {
-        float mv[8];
-        load8<T>(reinterpret_cast<const T*>(p.mask) + n * (int)p.mN + y * (int)p.mH + x * (int)p.mW +
-                     py * (int)(p.mH >> 1) + pxx * (int)(p.mW >> 1) + co, mv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = mv[j] > 0.f ? v[j] : 0.f;
-      }
-      if (has_bnb) {
-        float cv[8];
-        load8<T>(reinterpret_cast<const T*>(p.bnb_x) + dof + co, cv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { s1[j] += v[j]; s2[j] += v[j] * cv[j]; }
-      }
+      epi_value<T, 8>(v, opt, k, p.addend,
+                      n * (int)p.aN + y * (int)p.aH + x * (int)p.aW + py * (int)(p.aH >> 1) + pxx * (int)(p.aW >> 1) + co,
+                      p.mask,
+                      n * (int)p.mN + y * (int)p.mH + x * (int)p.mW + py * (int)(p.mH >> 1) + pxx * (int)(p.mW >> 1) + co,
+                      p.bnb_x, dof + co, s1, s2);
       store8<T>(reinterpret_cast<T*>(p.dst) + dof + co, v);
     }
     t32_wave_sync();
@@ -266,59 +245,17 @@ __global__ __launch_bounds__(256, 3) void conv3x3_s2d_kernel(const FsDual<FsConv
     const float tot = t32_reduce16_row(sv, lane);
     const int j = ((lane >> 1) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 3) & 1);
     red[(wave * CO + cs * 8 + j) * 2 + (lane & 1)] = tot;
-    t32_barrier();
-    if (t < CO) {
-      float u = 0.f, w = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { u += red[(k * CO + t) * 2]; w += red[(k * CO + t) * 2 + 1]; }
-      const int c = co0 + t;
-      if (c < p.Co) {
-        const long sg = p.stat_group_rows > 0 ? fs_div(n, g.dIPG) : 0;
-        double* sl = p.stats + (sg * FS_STAT_SLOTS + px % FS_STAT_SLOTS) * 2 * p.Co;
-        const double wd = ((double)w - (double)p.bnb_mean[sg * p.Co + c] * (double)u) * (double)p.bnb_invstd[sg * p.Co + c];
-        atomicAdd(sl + c, (double)u);
-        atomicAdd(sl + p.Co + c, wd);
-      }
-    }
+    conv_lds_barrier();
+    epi_stats_tail<CO, 4>(red, t, co0, p.Co, p.stats, p.stat_group_rows > 0 ? fs_div(n, g.dIPG) : 0, px, p.bnb_mean, p.bnb_invstd);
   }
 }
 
-// tile of dY positions (TH x TW <= 128, halo (TH+1) x (TW+1) <= S2D_HMAX) that wastes the fewest MFMA lanes
-inline S2dGeom s2d_pick_geom(int Hd, int Wd) {
-  S2dGeom best{};
-  double best_cost = 1e30;
-  for (int tw = std::min(4, Wd); tw <= std::min(Wd, 64); ++tw) {
-    const int th = std::min(S2D_PIX / tw, Hd);
-    if (th < 1 || (th + 1) * (tw + 1) > S2D_HMAX) continue;
-    const int tx = (Wd + tw - 1) / tw, ty = (Hd + th - 1) / th;
-    const double waste = (double)tx * ty * S2D_PIX / ((double)Hd * Wd);
-    const double halo = (double)(th + 1) * (tw + 1) / ((double)th * tw);
-    double cost = waste * (1.0 + 0.15 * halo);
-    if (tw % 32 != 0 && tw != Wd) cost *= 1.02;
-    if (cost < best_cost - 1e-9) { best_cost = cost; best.TH = th; best.TW = tw; best.tiles_x = tx; best.tiles_y = ty; }
-  }
-  if (best.TW > 0) {
-    best.mTW = fs_div_magic(best.TW); best.mHW = fs_div_magic(best.TW + 1);
-    best.dTX = fs_make_div(best.tiles_x); best.dTY = fs_make_div(best.tiles_y);
-  }
-  return best;
-}
+// tile of dY positions (conv_epi.h): halo (TH+1) x (TW+1) <= S2D_HMAX, 32-wide tiles preferred
+inline S2dGeom s2d_pick_geom(int Hd, int Wd) { return conv_pick_tile<S2dGeom>(Hd, Wd, S2D_PIX, S2D_HMAX, 1, true); }
 
 int s2d_problem(const FsConvArgs& a, S2dGeom& g) {
   g = s2d_pick_geom(a.Hd, a.Wd);
-  if (g.TH == 0) return 0;
-  g.dIPG = FsDiv{0u, 0u};
-  if (a.stat_group_rows > 0) {
-    const long hw = (long)a.Hd * a.Wd;
-    if (a.stat_group_rows % hw != 0) return 0;
-    g.dIPG = fs_make_div((int)(a.stat_group_rows / hw));
-  }
-  const int npix = a.N * g.tiles_x * g.tiles_y, nco = a.Co_p / S2D_CO;
-  int blocks = npix * nco;
-  g.pix_major = (nco > 1 && a.src_bytes > 2 * a.wgt_bytes) ? 1 : 0;
-  if (g.pix_major) blocks = 8 * ((npix + 7) / 8) * nco;
-  else if (nco % 8 != 0 && 8 % nco == 0) { const int q = 8 / nco; blocks = 8 * ((npix + q - 1) / q); }
-  return blocks;
+  return conv_tile_grid(a, g, S2D_CO);
 }
 
 template <typename T, int EP, bool DS>

@@ -73,17 +73,9 @@ __global__ __launch_bounds__(256, t32_minwaves(PIX, CO, EP, PRO)) void conv3x3_t
   const int nhalo = HH * HW;
   const int ntile = g.TH * g.TW;
 
-  // ---- tile mapping (XCD-aware, as conv3x3_halo.hip) ----
-  const int npix = p.N * g.tiles_y * g.tiles_x, nco = p.Co_p / CO;
+  // ---- tile mapping: XCD-aware (conv_epi.h) ----
   int px, cy;
-  {
-    const int id = bid, xcd = id & 7, slot = id >> 3;
-    if (g.pix_major) { cy = slot % nco; px = (slot / nco) * 8 + xcd; }
-    else if (nco % 8 == 0) { const int q = nco >> 3; cy = xcd + 8 * (slot % q); px = slot / q; }
-    else if (8 % nco == 0) { const int q = 8 / nco; cy = xcd % nco; px = slot * q + xcd / nco; }
-    else { cy = id % nco; px = id / nco; }
-    if (px >= npix) return;
-  }
+  if (!conv_xcd_tile(bid, p.Co_p / CO, p.N * g.tiles_y * g.tiles_x, g.pix_major, px, cy)) return;
   const int tq = fs_div(px, g.dTX); const int tx_i = px - tq * g.tiles_x;
   const int n = fs_div(tq, g.dTY); const int ty_i = tq - n * g.tiles_y;
   const int y0 = ty_i * g.TH, x0 = tx_i * g.TW;
@@ -193,9 +185,9 @@ __global__ __launch_bounds__(256, t32_minwaves(PIX, CO, EP, PRO)) void conv3x3_t
     pro_build_table<PRO>(p, t32_pro_tab, pgrp, t, 256);
   }
   for (int cc = 0; cc < nchunk; ++cc) {
-    t32_barrier();                 // previous chunk fully multiplied (first pass: the coefficient table is complete)
+    conv_lds_barrier();                 // previous chunk fully multiplied (first pass: the coefficient table is complete)
     store_lds(cc);
-    t32_barrier();
+    conv_lds_barrier();
     if (cc + 1 < nchunk) load_regs(cc + 1);
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
@@ -216,20 +208,21 @@ __global__ __launch_bounds__(256, t32_minwaves(PIX, CO, EP, PRO)) void conv3x3_t
     }
   }
 
-  // ---- epilogue ----
+  // ---- epilogue (conv_epi.h's pipeline on 8 channels of one pixel, read back through the wave's LDS region) ----
   const bool has_bias = T32_FLAG(EP_BIAS, p.bias != nullptr);
-  const bool has_add = T32_FLAG(EP_ADDEND, p.addend != nullptr);
-  const bool has_relu = T32_FLAG(EP_RELU, p.relu != 0);
-  const bool has_mask = T32_FLAG(EP_MASK, p.mask != nullptr);
   const bool has_bnb = T32_FLAG(EP_BNB, p.bnb_x != nullptr);
   const bool has_stats = T32_FLAG(EP_STATS | EP_BNB, p.stats != nullptr);
   const bool has_mbn = T32_FLAG(EP_MASKBN, p.bnb_scale != nullptr);
   const bool f32out = T32_FLAG(EP_F32, p.out_f32 != 0);
+  // (the bias vector is zero when there is none and always added; sums only where statistics leave the block)
+  const EpiOpt opt{true, T32_FLAG(EP_ADDEND, p.addend != nullptr), T32_FLAG(EP_RELU, p.relu != 0),
+                   T32_FLAG(EP_MASK, p.mask != nullptr), has_bnb, has_mbn, has_stats};
 
-  t32_barrier();                                     // every wave is done with the operand buffer
+  conv_lds_barrier();                                // every wave is done with the operand buffer
   float* ep = reinterpret_cast<float*>(lds + wave * (WPIX * EPS));
   const int l15 = lane & 15, cs = lane >> 4;         // read-back: pixel l15 (+16 i), channels cs*8 .. cs*8+7 of a tile
-  const int sgoff = p.stat_group_rows > 0 ? fs_div(n, g.dIPG) * p.Co : 0;
+  const int sg = p.stat_group_rows > 0 ? fs_div(n, g.dIPG) : 0;
+  const int sgoff = sg * p.Co;
   constexpr int NI = WPIX / 16;
   int doff[NI];
 #pragma unroll
@@ -257,11 +250,12 @@ __global__ __launch_bounds__(256, t32_minwaves(PIX, CO, EP, PRO)) void conv3x3_t
     const int co = co0 + a * 32 + cs * 8;
     const bool cok = co < p.Co;                      // (Co % 8 == 0 on this path)
     const int cof = cok ? co : 0;
-    float bv[8], msc[8], msh[8], s1[8], s2[8];
+    EpiCh<8> k{};
+    float s1[8], s2[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { bv[j] = 0.f; msc[j] = 0.f; msh[j] = 0.f; s1[j] = 0.f; s2[j] = 0.f; }
-    if (has_bias) load8<float>(p.bias + cof, bv);
-    if (has_mbn) { load8<float>(p.bnb_scale + sgoff + cof, msc); load8<float>(p.bnb_shift + sgoff + cof, msh); }
+    for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+    if (has_bias) epi_load_ch(p.bias + cof, k.bias);
+    if (has_mbn) { epi_load_ch(p.bnb_scale + sgoff + cof, k.scale); epi_load_ch(p.bnb_shift + sgoff + cof, k.shift); }
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const float* rp = ep + ((i * 16 + l15) * EPS + 2 * cs) * 4;
@@ -269,38 +263,10 @@ __global__ __launch_bounds__(256, t32_minwaves(PIX, CO, EP, PRO)) void conv3x3_t
       if (doff[i] < 0 || !cok) continue;
       const int y = doff[i] >> 16, x = doff[i] & 0xffff;
       const int dof = n * (int)p.dN + y * (int)p.dH + x * (int)p.dW;
-      float v[8] = {v0.x + bv[0], v0.y + bv[1], v0.z + bv[2], v0.w + bv[3], v1.x + bv[4], v1.y + bv[5], v1.z + bv[6], v1.w + bv[7]};
-      if (has_add) {
-        float av[8];
-        load8<T>(reinterpret_cast<const T*>(p.addend) + n * (int)p.aN + y * (int)p.aH + x * (int)p.aW + co, av);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] += av[j];
-      }
-      if (has_relu) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
-      }
-      if (has_mask) {
-        float mv[8];
-        load8<T>(reinterpret_cast<const T*>(p.mask) + n * (int)p.mN + y * (int)p.mH + x * (int)p.mW + co, mv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = mv[j] > 0.f ? v[j] : 0.f;
-      }
-      if (has_bnb) {
-        // BatchNorm-backward sums: (sum g, sum g*x) here; sum g*xhat = (sum g*x - mean * sum g) * invstd is formed in
-        // f64 when the block's partials are added to the slots
-        float cv[8];
-        load8<T>(reinterpret_cast<const T*>(p.bnb_x) + dof + co, cv);       // same layout as dst
-        if (has_mbn) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = (cv[j] * msc[j] + msh[j]) > 0.f ? v[j] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { s1[j] += v[j]; s2[j] += v[j] * cv[j]; }
-      } else if (has_stats) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { s1[j] += v[j]; s2[j] += v[j] * v[j]; }
-      }
+      float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+      // (BatchNorm-backward sums: (sum g, sum g*x) here; the tail forms sum g*xhat in f64.  bnb_x: same layout as dst)
+      epi_value<T, 8>(v, opt, k, p.addend, n * (int)p.aN + y * (int)p.aH + x * (int)p.aW + co,
+                      p.mask, n * (int)p.mN + y * (int)p.mH + x * (int)p.mW + co, p.bnb_x, dof + co, s1, s2);
       if (f32out) store8<float>(reinterpret_cast<float*>(p.dst) + dof + co, v);
       else store8<T>(reinterpret_cast<T*>(p.dst) + dof + co, v);
     }
@@ -316,21 +282,8 @@ __global__ __launch_bounds__(256, t32_minwaves(PIX, CO, EP, PRO)) void conv3x3_t
     t32_wave_sync();                                 // read-back done before the next tile overwrites the region
   }
   if (has_stats) {
-    t32_barrier();
-    if (t < CO) {
-      float u = 0.f, w = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { u += red[(k * CO + t) * 2]; w += red[(k * CO + t) * 2 + 1]; }
-      const int co = co0 + t;
-      if (co < p.Co) {
-        const long sg = p.stat_group_rows > 0 ? fs_div(n, g.dIPG) : 0;
-        double* sl = p.stats + (sg * FS_STAT_SLOTS + px % FS_STAT_SLOTS) * 2 * p.Co;
-        double wd = (double)w;
-        if (has_bnb) wd = (wd - (double)p.bnb_mean[sg * p.Co + co] * (double)u) * (double)p.bnb_invstd[sg * p.Co + co];
-        atomicAdd(sl + co, (double)u);
-        atomicAdd(sl + p.Co + co, wd);
-      }
-    }
+    conv_lds_barrier();
+    epi_stats_tail<CO, 4>(red, t, co0, p.Co, p.stats, sg, px, has_bnb ? p.bnb_mean : nullptr, p.bnb_invstd);
   }
   // (last, so that its arguments are not live across the walk: saved statistics / running statistics / dgamma, dbeta)
   if constexpr (PRO != 0) { if (bid == 0) pro_block0<PRO>(p, t, 256); }
@@ -340,20 +293,8 @@ __global__ __launch_bounds__(256, t32_minwaves(PIX, CO, EP, PRO)) void conv3x3_t
 template <int PIX, int CO>
 int t32_problem(const FsConvArgs& a, T32Geom& g) {
   g = t32_pick_geom(a.Hd, a.Wd, PIX, t32_hmax(PIX));
-  if (g.TH == 0) return 0;
-  g.dIPG = FsDiv{0u, 0u}; g.dPRG = FsDiv{0u, 0u};
-  if (a.stat_group_rows > 0) {
-    const long hw = (long)a.Hd * a.Wd;
-    if (a.stat_group_rows % hw != 0) return 0;
-    g.dIPG = fs_make_div((int)(a.stat_group_rows / hw));
-  }
   if (a.pro_group_imgs > 0) g.dPRG = fs_make_div(a.pro_group_imgs);
-  const int npix = a.N * g.tiles_x * g.tiles_y, nco = a.Co_p / CO;
-  int blocks = npix * nco;
-  g.pix_major = (nco > 1 && a.src_bytes > 2 * a.wgt_bytes) ? 1 : 0;
-  if (g.pix_major) blocks = 8 * ((npix + 7) / 8) * nco;
-  else if (nco % 8 != 0 && 8 % nco == 0) { const int q = 8 / nco; blocks = 8 * ((npix + q - 1) / q); }
-  return blocks;
+  return conv_tile_grid(a, g, CO);
 }
 
 template <typename T, int PIX, int CO, int EP, int PRO>

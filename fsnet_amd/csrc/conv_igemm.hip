@@ -23,9 +23,7 @@
 //   * with kg = 8 one address computation feeds four 16-byte loads (a 64-byte unit of one tap).
 // The same kernel computes dgrad: source = dY, packed weights Wt[ci][r][s][co], taps walked with
 // sgn = -1, plus a parity test and halved strides for stride 2.
-#include "common.h"
-#include "fsnet_hip_internal.h"
-#include <algorithm>
+#include "conv_epi.h"
 
 namespace {
 
@@ -33,10 +31,6 @@ template <int KG> __device__ __forceinline__ int lds_swz(int row) {
   // XOR swizzle of the 16-byte group index that makes the ds_read_b128 lane groups conflict-free
   // (64-byte rows: 2 bits from row bit 3; 128-byte rows: 3 bits from row bits 1..3)
   return KG == 4 ? (((row >> 3) & 1) << 1) : ((row >> 1) & 7);
-}
-
-__device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0));
 }
 
 struct IgGeom { FsDiv dW, dH; };
@@ -78,17 +72,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const FsDual<FsConvArgs
   const int n0 = p.grp_imgs > 0 ? (int)blockIdx.z * p.grp_imgs : 0;
   const int nch = p.ncls > 1 ? p.cls_nch[cls] : p.nchunks;
 
-  // XCD-aware tile mapping (block b runs on XCD b % 8, each XCD has a private 4 MB L2): all pixel tiles of one
-  // channel tile go to the same XCD(s), so a weight tile is fetched from HBM/MALL once per XCD and then hit in L2.
-  int px, cy;
-  {
-    const int npix = (p.M + PIX - 1) / PIX, nco = p.Co_p / CO;
-    const int id = bid, xcd = id & 7, slot = id >> 3;
-    if (nco % 8 == 0) { const int g = nco >> 3; cy = xcd + 8 * (slot % g); px = slot / g; }
-    else if (8 % nco == 0) { const int g = 8 / nco; cy = xcd % nco; px = slot * g + xcd / nco; }
-    else { cy = id % nco; px = id / nco; }
-    if (px >= npix) return;
-  }
+  int px, cy;     // XCD-aware tile mapping (conv_epi.h)
+  if (!conv_xcd_tile(bid, p.Co_p / CO, (p.M + PIX - 1) / PIX, 0, px, cy)) return;
 
   {
     const int2* kt = reinterpret_cast<const int2*>(p.ktab) + (p.ncls > 1 ? p.cls_ktab_off[cls] : 0);
@@ -146,13 +131,13 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const FsDual<FsConvArgs
                 ((unsigned)(h >> p.dshift) < (unsigned)p.Hs) && ((unsigned)(w >> p.dshift) < (unsigned)p.Ws);
       int voff = ok ? pvoff[i] + e.x : OOB;
 #pragma unroll
-      for (int j = 0; j < UG; ++j) rp[i][j] = buf_load16(rs_src, voff + j * 16);
+      for (int j = 0; j < UG; ++j) rp[i][j] = conv_load16(rs_src, voff + j * 16);
     }
 #pragma unroll
     for (int i = 0; i < LCU; ++i) {
       int voff = wvoff[i] == OOB ? OOB : wvoff[i] + kc * stage_bytes;
 #pragma unroll
-      for (int j = 0; j < UG; ++j) rc[i][j] = buf_load16(rs_wgt, voff + j * 16);
+      for (int j = 0; j < UG; ++j) rc[i][j] = conv_load16(rs_wgt, voff + j * 16);
     }
   };
   auto store_lds = [&](int buf, const uint4 (&rp)[LPU][UG], const uint4 (&rc)[LCU][UG]) {
@@ -234,14 +219,17 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const FsDual<FsConvArgs
     __syncthreads();
   }
 
-  // ---- epilogue: lane holds, for pixel (tile b, li), channels lg*4..lg*4+3 of channel tile a ----
+  // ---- epilogue: lane holds, for pixel (tile b, li), channels lg*4..lg*4+3 of channel tile a.  The 4-channel value
+  // pipeline in this kernel's own lines (channel-only operands loaded per pixel, at the point of use); conv_epi.h states
+  // the 8-channel one and the statistics tail ----
   float s1[TC][4], s2[TC][4];
 #pragma unroll
   for (int a = 0; a < TC; ++a)
 #pragma unroll
     for (int j = 0; j < 4; ++j) { s1[a][j] = 0.f; s2[a][j] = 0.f; }
-  const long sgoff = p.grp_imgs > 0 ? (long)blockIdx.z * p.Co
-                                    : (p.stat_group_rows > 0 ? (long)(pix0 / p.stat_group_rows) * p.Co : 0);
+  // statistics group of this tile (groups are multiples of the tile height: fs_conv_igemm checks)
+  const long sg = p.grp_imgs > 0 ? (long)blockIdx.z : (p.stat_group_rows > 0 ? (long)(pix0 / p.stat_group_rows) : 0);
+  const long sgoff = sg * p.Co;
 
 #pragma unroll
   for (int b = 0; b < TP; ++b) {
@@ -300,45 +288,17 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const FsDual<FsConvArgs
   }
 
   if (p.stats) {
-    // per-channel (sum, sumsq): 16 pixel lanes by shuffle, the WP pixel-waves through LDS, then ONE f64
-    // atomic per channel per block into one of FS_STAT_SLOTS address slots (same-address atomics cost
-    // ~12 ns each on MI355X; slots + block reduce keep the chain per address short).
     __syncthreads();                     // all waves are done reading the operand tiles
     float* red = reinterpret_cast<float*>(&lds_p[0][0]);   // [WP][CO][2]
-#pragma unroll
-    for (int a = 0; a < TC; ++a)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float u = s1[a][j], w = s2[a][j];
-        u = row16_sum(u); w = row16_sum(w);     // over the 16 pixel lanes of this channel (DPP, no LDS)
-        if (li == 0) {
-          int cl = wc * WCO + a * 16 + lg * 4 + j;
-          red[(wp * CO + cl) * 2] = u; red[(wp * CO + cl) * 2 + 1] = w;
-        }
-      }
+    epi_row_sums<TC>(s1, s2, red + wp * CO * 2, wc * WCO, li, lg);
     __syncthreads();
-    if (t < CO) {
-      float u = 0.f, w = 0.f;
-#pragma unroll
-      for (int k = 0; k < WP; ++k) { u += red[(k * CO + t) * 2]; w += red[(k * CO + t) * 2 + 1]; }
-      int co = co0 + t;
-      if (co < p.Co) {
-        // statistics group of this tile (groups are multiples of the tile height: fs_conv_igemm checks)
-        const long sg = p.grp_imgs > 0 ? (long)blockIdx.z : (p.stat_group_rows > 0 ? pix0 / p.stat_group_rows : 0);
-        double* sl = p.stats + (sg * FS_STAT_SLOTS + px % FS_STAT_SLOTS) * 2 * p.Co;
-        atomicAdd(sl + co, (double)u);
-        atomicAdd(sl + p.Co + co, (double)w);
-      }
-    }
+    epi_stats_tail<CO, WP>(red, t, co0, p.Co, p.stats, sg, px);
   }
 }
 
 template <int PIX, int CO>
 int igemm_blocks(const FsConvArgs& a) {
-  const int npix = (a.M + PIX - 1) / PIX, nco = a.Co_p / CO;
-  int blocks = npix * nco;
-  if (nco % 8 != 0 && 8 % nco == 0) { const int g = 8 / nco; blocks = 8 * ((npix + g - 1) / g); }
-  return blocks;
+  return conv_xcd_blocks((a.M + PIX - 1) / PIX, a.Co_p / CO, 0);
 }
 
 // b != nullptr: a second problem of the same shape class in the same launch
@@ -401,6 +361,7 @@ int igemm_check(const FsConvArgs* args) {
   if (args->dshift && ((args->sH | args->sW) & 1)) return FS_EINVAL;
   if (args->stats && args->stat_group_rows > 0 && args->stat_group_rows % 256 != 0) return FS_EINVAL;
   if (args->grp_imgs > 0 && (args->N <= 0 || args->N % args->grp_imgs != 0)) return FS_EINVAL;
+  if (args->bnb_scale) return FS_EINVAL;      // the derived ReLU mask exists in the 3x3 kernels only (fs_conv3x3_halo)
   return FS_OK;
 }
 // everything that selects an instantiation or the grid's y extent must agree

@@ -12,19 +12,13 @@
 //     (2y + r, 2x + 4j + lg); the non-existent tap s = 7 gets a zero weight fragment;
 //   * BatchNorm statistics accumulate in registers over the block's tiles and leave as one f64 atomic per channel.
 // Input bytes per output pixel drop from 784 to ~97.
-#include "common.h"
-#include "fsnet_hip_internal.h"
-#include <algorithm>
+#include "conv_epi.h"
 
 namespace {
 
 constexpr int TY = 8, TX = 16;                 // output tile: 8 rows x 16 pixels
 constexpr int PH = 2 * TY + 5, PW = 2 * TX + 6; // input patch rows / row pitch (one spare pixel: tap s = 7 of x = 15)
 constexpr int CO = 64, TAPS = 49;
-
-__device__ __forceinline__ uint4 stem_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0));
-}
 
 struct StemFwdGeom { int tiles_x, tiles_y, ntiles, tiles_per_block; FsDiv dTX, dTY, dIPG; };
 
@@ -51,7 +45,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(const FsDual<FsConvArgs,
   const int wrow_bytes = p.nchunks * p.kg * 16;          // packed forward operand: [co][tap][8 ch], K padded
   for (int i = t; i < CO * TAPS; i += 256) {
     const int co = i / TAPS, tap = i - co * TAPS;
-    lds_w[i] = stem_load16(rs_wgt, co * wrow_bytes + tap * 16);
+    lds_w[i] = conv_load16(rs_wgt, co * wrow_bytes + tap * 16);
   }
 
   float s1[4][4], s2[4][4];
@@ -67,26 +61,13 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(const FsDual<FsConvArgs,
     // [wave][co][2] through the patch buffer (free between tiles), then one f64 atomic per channel and moment
     __syncthreads();
     float* red = reinterpret_cast<float*>(&lds_x[0]);
+    epi_row_sums<4>(s1, s2, red + wave * CO * 2, 0, li, lg);
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float u = row16_sum(s1[c][j]), w = row16_sum(s2[c][j]);
-        if (li == 0) {
-          const int co = c * 16 + lg * 4 + j;
-          red[(wave * CO + co) * 2] = u; red[(wave * CO + co) * 2 + 1] = w;
-        }
-        s1[c][j] = 0.f; s2[c][j] = 0.f;
-      }
+      for (int j = 0; j < 4; ++j) { s1[c][j] = 0.f; s2[c][j] = 0.f; }
     __syncthreads();
-    if (t < CO && t < p.Co) {
-      float u = 0.f, w = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { u += red[(k * CO + t) * 2]; w += red[(k * CO + t) * 2 + 1]; }
-      double* sl = p.stats + ((long)group * FS_STAT_SLOTS + bid % FS_STAT_SLOTS) * 2 * p.Co;
-      atomicAdd(sl + t, (double)u);
-      atomicAdd(sl + p.Co + t, (double)w);
-    }
+    epi_stats_tail<CO, 4>(red, t, 0, p.Co, p.stats, group, bid);
     __syncthreads();
   };
 
@@ -106,7 +87,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(const FsDual<FsConvArgs,
       const int py = i / PW, px = i - py * PW;
       const int sy = 2 * y0 - 3 + py, sx = 2 * x0 - 3 + px;
       const bool ok = (unsigned)sy < (unsigned)p.Hs && (unsigned)sx < (unsigned)p.Ws;
-      lds_x[i] = stem_load16(rs_src, ok ? (int)(((long)n * p.sN + (long)sy * p.sH + (long)sx * p.sW) * 2) : OOB);
+      lds_x[i] = conv_load16(rs_src, ok ? (int)(((long)n * p.sN + (long)sy * p.sH + (long)sx * p.sW) * 2) : OOB);
     }
     __syncthreads();
 

@@ -1,25 +1,13 @@
-// Pieces of the 32x32-MFMA-tile 3x3 convolution kernel (conv3x3_t32.hip): operand units,
-// 16-byte epilogue accessors, the v_permlane32_swap accumulator transposition and the halving statistics reduction.
+// Pieces of the 32x32-MFMA-tile 3x3 convolution kernels (conv3x3_t32.hip, conv3x3_s2d.hip) on top of conv_epi.h: operand
+// units, the v_permlane32_swap accumulator transposition and the halving statistics reduction.
 #pragma once
-#include "common.h"
-#include "fsnet_hip_internal.h"
-#include <algorithm>
+#include "conv_epi.h"
 #include <cstdlib>
 
 namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-__device__ __forceinline__ uint4 t32_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0));
-}
-
-// workgroup barrier that orders LDS traffic only (no vmcnt drain: the next chunk's global loads stay in flight)
-__device__ __forceinline__ void t32_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 __device__ __forceinline__ void t32_wave_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 struct T32Geom {
@@ -48,24 +36,6 @@ template <> struct Mma32<float> {
     for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(va[j], vb[j], acc, 0, 0, 0);
   }
 };
-
-// 8 consecutive channels of one pixel <-> floats (epilogue side)
-template <typename T> __device__ __forceinline__ void load8(const T* p, float* v);
-template <> __device__ __forceinline__ void load8<bf16>(const bf16* p, float* v) {
-  Unit<bf16>::unpack(*reinterpret_cast<const uint4*>(p), v);
-}
-template <> __device__ __forceinline__ void load8<float>(const float* p, float* v) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-template <typename T> __device__ __forceinline__ void store8(T* p, const float* v);
-template <> __device__ __forceinline__ void store8<bf16>(bf16* p, const float* v) {
-  *reinterpret_cast<uint4*>(p) = Unit<bf16>::pack(v);
-}
-template <> __device__ __forceinline__ void store8<float>(float* p, const float* v) {
-  reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-  reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-}
 
 #define T32_FLAG(bit, rt) (EP < 0 ? (rt) : ((EP & (bit)) != 0))
 
@@ -109,15 +79,7 @@ __device__ __forceinline__ float t32_reduce16_row(const float* v, int lane) {
   return t32_xadd<0xB1>(b0 ? w2[1] : w2[0], b0 ? w2[0] : w2[1]);
 }
 __device__ __forceinline__ float t32_reduce16(const float* v, int lane) {
-  const bool b3 = lane & 8, b2 = lane & 4, b1 = lane & 2, b0 = lane & 1;
-  float w8[8], w4[4], w2[2];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) w8[k] = t32_xadd<0x140>(b3 ? v[2 * k + 1] : v[2 * k], b3 ? v[2 * k] : v[2 * k + 1]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) w4[k] = t32_xadd<0x141>(b2 ? w8[2 * k + 1] : w8[2 * k], b2 ? w8[2 * k] : w8[2 * k + 1]);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) w2[k] = t32_xadd<0x4E>(b1 ? w4[2 * k + 1] : w4[2 * k], b1 ? w4[2 * k] : w4[2 * k + 1]);
-  const float w1 = t32_xadd<0xB1>(b0 ? w2[1] : w2[0], b0 ? w2[0] : w2[1]);
+  const float w1 = t32_reduce16_row(v, lane);
   // rows 1, 3 of x <-> rows 0, 2 of y (inline asm for the same reason as t32_swap32)
   float x = w1, y = w1;
   asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x), "+v"(y));
@@ -137,39 +99,8 @@ __device__ __forceinline__ void t32_sched_step() {
   }
 }
 
-// pixel tile (TH x TW <= PIX, halo <= hmax) that wastes the fewest MFMA lanes; wide tiles preferred (a 32-pixel
-// MFMA tile that is one image row reads its halo conflict-free)
-inline T32Geom t32_pick_geom(int Hd, int Wd, int PIX, int hmax) {
-  T32Geom best{};
-  double best_cost = 1e30;
-  for (int tw = std::min(4, Wd); tw <= std::min(Wd, 64); ++tw) {
-    const int th = std::min(PIX / tw, Hd);
-    if (th < 1 || (th + 2) * (tw + 2) > hmax) continue;
-    const int tx = (Wd + tw - 1) / tw, ty = (Hd + th - 1) / th;
-    const double waste = (double)tx * ty * PIX / ((double)Hd * Wd);
-    const double halo = (double)(th + 2) * (tw + 2) / ((double)th * tw);
-    double cost = waste * (1.0 + 0.15 * halo);
-    if (tw % 32 != 0 && tw != Wd) cost *= 1.02;
-    if (cost < best_cost - 1e-9) { best_cost = cost; best.TH = th; best.TW = tw; best.tiles_x = tx; best.tiles_y = ty; }
-  }
-  if (best.TW > 0) {
-    best.mTW = fs_div_magic(best.TW); best.mHW = fs_div_magic(best.TW + 2);
-    best.dTX = fs_make_div(best.tiles_x); best.dTY = fs_make_div(best.tiles_y);
-  }
-  return best;
-}
-
-inline int t32_cu_count() {
-  static const int n = [] {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-      hipDeviceProp_t pr;
-      if (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount;
-    }
-    return cus;
-  }();
-  return n;
-}
+// pixel tile (conv_epi.h): a 2-pixel halo border, 32-wide tiles preferred
+inline T32Geom t32_pick_geom(int Hd, int Wd, int PIX, int hmax) { return conv_pick_tile<T32Geom>(Hd, Wd, PIX, hmax, 2, true); }
 
 inline int t32_ep_mask(const FsConvArgs& a) {
   int m = 0;

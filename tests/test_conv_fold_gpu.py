@@ -108,13 +108,25 @@ def test_weight_gradient_with_batchnorm_prologue_matches_autograd(dev, case):
     assert (dw.cpu() - 2 * w.grad).abs().max().item() <= 4e-3 * wscale
 
 
-@pytest.mark.parametrize("case", FOLD_CASES)
+# the same data gradient where the launch stays on the 16x16-tile kernel (too few 256-pixel tiles for the 32x32-tile one:
+# layers 3 / 4 of the encoders in the benchmark step) — (case, pixel tile, channel tile) as fs_conv3x3_halo_plan reports them
+HALO_MASK_CASES = [
+    ((256, 256, 4, 12, 40, 2), 128, 16),     # two statistics groups, ragged 12 x 40 images
+    ((64, 64, 4, 32, 128, 2), 128, 32),
+]
+
+
+@pytest.mark.parametrize("case", FOLD_CASES + [c for c, _, _ in HALO_MASK_CASES])
 def test_data_gradient_with_derived_relu_mask_matches_autograd(dev, case):
     """dgrad(bn_fuse=(c, st, sums), mask_bn=True): dx = conv_transpose(dy) where scale*c + shift > 0, else 0, and
     sums = (sum dx, sum dx * xhat), xhat = (c - mean) * invstd, per statistics group"""
     from fsnet_amd.hip import ops
     from fsnet_amd.hip.conv import ConvOp
     Ci, Co, N, H, W, G = case
+    for hc, pix, cot in HALO_MASK_CASES:
+        if hc == case:
+            plan = ConvOp(Ci, Co, 3, 3, 1, 1, torch.bfloat16, dev).plan_3x3(N, H, W, forward=False)
+            assert (plan["kernel"], plan["pix"], plan["co"]) == ("halo", pix, cot), plan
     g = torch.Generator().manual_seed(300 + Ci + N)
     w = _bf(torch.randn(Co, Ci, 3, 3, generator=g) / (9 * Ci) ** 0.5)
     dy = _bf(torch.randn(N, H, W, Co, generator=g))
@@ -533,3 +545,49 @@ def test_persistent_one_chunk_kernel_statistic_groups(dev, monkeypatch):
         big = max(r0.abs().max().item(), r1.abs().max().item())
         eps = 2e-3 * big + 1e-3 * gref[sl].double().norm().item() / Ci ** 0.5
         assert (ss[k, 0] - r0).abs().max().item() <= eps and (ss[k, 1] - r1).abs().max().item() <= eps
+
+
+def test_halo_kernel_256_pixel_tile_against_conv2d(dev, monkeypatch):
+    """conv3x3_halo.hip's 256 x 16 tile: 16 output channels and at least 1024 pixel tiles — the depth decoder's full-resolution
+    16-channel layers (depth_encoder.py:45-63) whenever the persistent one-chunk kernel does not take them (forced here through
+    FsConvArgs.force_impl = 1).  Forward with bias + statistics + fp32 output and the data gradient with addend / ReLU mask /
+    BatchNorm-backward sums, with the bounds of test_persistent_one_chunk_kernel_against_conv2d."""
+    from fsnet_amd.hip import ops
+    from fsnet_amd.hip.conv import ConvOp
+    from fsnet_amd.hip import conv as _conv
+    monkeypatch.setattr(_conv, "FORCE_3X3", 1)
+    dtype, Ci, Co, N, H, W = torch.bfloat16, 16, 16, 3, 192, 512
+    g = torch.Generator().manual_seed(1256)
+    x, gy = _bf(torch.randn(N, Ci, H, W, generator=g)), _bf(torch.randn(N, Co, H, W, generator=g))
+    w = _bf(torch.randn(Co, Ci, 3, 3, generator=g) / 12.0)
+    b = torch.randn(Co, generator=g)
+    op = ConvOp(Ci, Co, 3, 3, 1, 1, dtype, dev)
+    op.pack(w.to(dev).contiguous())
+    for fwd in (True, False):
+        plan = op.plan_3x3(N, H, W, forward=fwd)
+        assert (plan["kernel"], plan["pix"], plan["co"]) == ("halo", 256, 16), plan
+    xd, gyd = _nhwc(x, dev, dtype), _nhwc(gy, dev, dtype)
+    stats = torch.zeros(8, 2, Co, dtype=torch.float64, device=dev)
+    y = op.forward(xd, bias=b.to(dev), stats=stats, out_f32=True)
+    torch.cuda.synchronize()
+    y_ref = F.conv2d(x, w, b, padding=1)
+    ys = y_ref.abs().max().item()
+    assert (y.permute(0, 3, 1, 2).cpu() - y_ref).abs().max().item() <= 2e-3 * ys
+    s = stats.sum(0).cpu()
+    assert torch.allclose(s[0], y_ref.double().sum(dim=(0, 2, 3)), rtol=1e-3, atol=1e-3 * ys * (N * H * W) ** 0.5)
+    assert torch.allclose(s[1], (y_ref.double() ** 2).sum(dim=(0, 2, 3)), rtol=2e-3)
+    add, yact, cprev = (_bf(torch.randn(N, Ci, H, W, generator=g)) for _ in range(3))
+    st = ops.BnState(Ci, dev, 1)
+    mean, invstd = torch.randn(Ci, generator=g) * 0.1, torch.rand(Ci, generator=g) + 0.5
+    st.mean.copy_(mean); st.invstd.copy_(invstd); st.count = float(N * H * W)
+    sums = torch.zeros(8, 2, Ci, dtype=torch.float64, device=dev)
+    d = op.dgrad(gyd, H, W, addend=_nhwc(add, dev, dtype), mask=_nhwc(yact, dev, dtype), bn_fuse=(_nhwc(cprev, dev, dtype), st, sums))
+    torch.cuda.synchronize()
+    gref = torch.where(yact > 0, F.conv_transpose2d(gy, w, padding=1) + add, torch.zeros(()))
+    assert (d.float().permute(0, 3, 1, 2).cpu() - gref).abs().max().item() <= 1e-2 * gref.abs().max().item()
+    xh = (cprev - mean.view(1, -1, 1, 1)) * invstd.view(1, -1, 1, 1)
+    ss = sums.sum(0).cpu()
+    r0, r1 = gref.double().sum(dim=(0, 2, 3)), (gref.double() * xh.double()).sum(dim=(0, 2, 3))
+    big = max(r0.abs().max().item(), r1.abs().max().item())
+    eps = 2e-3 * big + 1e-3 * gref.double().norm().item() / Ci ** 0.5
+    assert (ss[0] - r0).abs().max().item() <= eps and (ss[1] - r1).abs().max().item() <= eps

@@ -219,6 +219,66 @@ def test_dgrad_epilogue_carries_bn_backward_sums(dev, case, dtype):
     assert float((dx2.float() - dx.float()).abs().max()) <= (1e-4 if dtype == torch.float32 else 5e-2) * float(dx.float().abs().max())
 
 
+@pytest.mark.parametrize("entry", ["fs_conv_igemm", "fs_conv1x1"])
+def test_1x1_entries_refuse_the_derived_relu_mask(dev, entry):
+    """FsConvArgs.bnb_scale (the ReLU mask derived from scale * bnb_x + shift) exists in the 3x3 kernels' epilogues only
+    (ConvOp.dgrad_spec asserts halo_d): the implicit GEMM and the 1x1 entry return FS_EINVAL instead of writing a gradient
+    that silently lacks the mask, and leave the destination alone."""
+    import ctypes as C
+    from fsnet_amd.hip import ops
+    from fsnet_amd.hip.binding import lib, stream_ptr
+    from fsnet_amd.hip.conv import ConvOp
+    dtype, Ci, Co, N, H, W = torch.bfloat16, 64, 64, 2, 8, 16
+    g = torch.Generator().manual_seed(41)
+    op = ConvOp(Ci, Co, 1, 1, 1, 0, dtype, dev, need_dgrad=True)
+    op.pack((torch.randn(Co, Ci, 1, 1, generator=g) / Ci ** 0.5).to(dev).contiguous())
+    dy = torch.randn(N, H, W, Co, generator=g).to(dev).to(dtype)
+    c = torch.randn(N, H, W, Ci, generator=g).to(dev).to(dtype)
+    st = ops.BnState(Ci, dev, 1)
+    st.mean.copy_(torch.randn(Ci, generator=g) * 0.1)
+    st.invstd.copy_(torch.rand(Ci, generator=g) + 0.5)
+    scale, shift = (torch.rand(Ci, generator=g) + 0.5).to(dev), (torch.randn(Ci, generator=g) * 0.3).to(dev)
+    sums = torch.zeros(8, 2, Ci, dtype=torch.float64, device=dev)
+    out = torch.full((N, H, W, Ci), -7.0, dtype=dtype, device=dev)
+    sp = op.dgrad_spec(dy, H, W, out=out, bn_fuse=(c, st, sums))
+    fn = getattr(lib, entry)
+    assert fn(C.byref(sp.a), sp.code, stream_ptr()) == 0          # the launch itself is one this entry takes ...
+    torch.cuda.synchronize()
+    assert not (out == -7).all()
+    out.fill_(-7.0)
+    sums.zero_()
+    sp.a.bnb_scale, sp.a.bnb_shift = scale.data_ptr(), shift.data_ptr()
+    assert fn(C.byref(sp.a), sp.code, stream_ptr()) == 1          # ... and FS_EINVAL with the derived mask
+    torch.cuda.synchronize()
+    assert (out == -7).all() and (sums == 0).all()
+
+
+def test_conv1x1_addend_relu_on_the_implicit_gemm(dev):
+    """fp32 1x1 convolutions run on the implicit GEMM (the 1x1 kernels are bf16): its epilogue's addend + ReLU with a
+    ragged last pixel tile and a partly filled channel tile (Co = 12 of Co_p = 16) — the pose decoder's 1x1 convolutions
+    of an fp32 run (pose_decoder.py:17-37).  Bound of test_conv_addend_relu_strided."""
+    from fsnet_amd.hip.conv import ConvOp
+    dtype = torch.float32
+    N, Ci, Co, H, W = 2, 32, 12, 6, 20
+    g = torch.Generator().manual_seed(8)
+    x = torch.randn(N, Ci, H, W, generator=g)
+    w = torch.randn(Co, Ci, 1, 1, generator=g) / 6
+    b = torch.randn(Co, generator=g)
+    add = torch.randn(N, Co, H, W, generator=g)
+    ref = F.relu(F.conv2d(x, w, b) + add)
+    op = ConvOp(Ci, Co, 1, 1, 1, 0, dtype, dev)
+    op.pack(w.to(dev))
+    sp = op.forward_spec(to_nhwc(x.to(dev), op.Ci_p, dtype), bias=torch.cat([b, torch.zeros(op.Co_p - Co)]).to(dev),
+                         addend=to_nhwc(add.to(dev), op.Co_p, dtype), relu=True)
+    assert sp.chain == ["conv_igemm"], sp.chain
+    from fsnet_amd.hip.conv import run_specs
+    run_specs([sp])
+    torch.cuda.synchronize()
+    got = sp.out[..., :Co].permute(0, 3, 1, 2).cpu()
+    assert (got - ref).abs().max().item() < 1e-4
+    assert sp.out[..., Co:].abs().max().item() == 0
+
+
 @pytest.mark.parametrize("Ci,N,H,W,groups", [(3, 2, 32, 64, 1), (6, 4, 64, 96, 2), (3, 3, 38, 70, 1), (6, 12, 192, 640, 2)])
 def test_stem_lds_kernel(dev, Ci, N, H, W, groups):
     """7x7/s2 stem through conv_stem.hip (LDS-resident weights, LDS im2col, persistent blocks): output and the

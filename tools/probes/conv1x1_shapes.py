@@ -1,7 +1,7 @@
 """1x1 convolutions of ResNet-50 at 320x1024, B=8: forward / data gradient per shape."""
 import sys; sys.path.insert(0, '.')
 import torch
-from fsnet_amd.hip.conv import ConvOp, USE_1X1
+from fsnet_amd.hip.conv import ConvOp
 dev = torch.device('cuda:0'); dt = torch.bfloat16
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 SHAPES = [("l1 64-64", 64, 64, 1, 80, 256), ("l1 64-256", 64, 256, 1, 80, 256), ("l1 256-64", 256, 64, 1, 80, 256),
@@ -23,7 +23,6 @@ def timeit(fn, n=20):
     for _ in range(5): g.replay()
     e.record(); torch.cuda.synchronize()
     return s.elapsed_time(e) / (5 * n) * 1e-3
-print("conv1x1 kernel:", USE_1X1)
 for name, Ci, Co, st, H, W in SHAPES:
     op = ConvOp(Ci, Co, 1, 1, st, 0, dt, dev)
     op.pack(torch.randn(Co, Ci, 1, 1, device=dev) * 0.05)
