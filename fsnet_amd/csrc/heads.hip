@@ -59,10 +59,29 @@ __device__ __forceinline__ void head_bwd_row(const float* __restrict__ logits, c
   }
 #pragma unroll
   for (int k = 0; k < K; ++k) { v[k] = fminf(fmaxf(raw[k], -10.f), 10.f); mx = fmaxf(mx, v[k]); }
-  float se = 0.f, sd = 0.f;
+  // The expectation d to well under an ulp without leaving float.  A confident pixel has one term near 1 and
+  // K - 1 small ones; a float running sum drops their low bits one by one (~sqrt(K)/2 ulp in se and d), and the dominant
+  // bin's (bin - d) below is a difference of near-equal numbers that turns those ulps into 1e-5 of the row's largest
+  // gradient element.  So: the denominator in two parts (terms >= 0.5 and the rest meet once), and d as the pair
+  // d0 + corr, corr from one pass over the residual sum_k e_k (bin_k - d0), whose terms are all small.
+  float seb = 0.f, ses = 0.f, sd = 0.f;
 #pragma unroll
-  for (int k = 0; k < K; ++k) { v[k] = expf(v[k] - mx); se += v[k]; sd += v[k] * sb[k]; }
-  float d = sd / se;
+  for (int k = 0; k < K; ++k) {
+    const float e = expf(v[k] - mx);
+    v[k] = e;
+    const bool big = e >= 0.5f;
+    seb += big ? e : 0.f;
+    ses += big ? 0.f : e;
+    sd += e * sb[k];
+  }
+  const float se = seb + ses;
+  const float d0 = sd / se;
+  float o[K];
+  float res = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) { o[k] = v[k] * (sb[k] - d0); res += o[k]; }
+  const float corr = res / se;
+  const float d = d0 + corr;
   float g = (d_depth ? d_depth[m] : 0.f);
   if (sc != 0.f) {
     // depth = d sc, disp = (1/depth - 1/(max sc)) / (1/(min sc) - 1/(max sc))
@@ -70,12 +89,11 @@ __device__ __forceinline__ void head_bwd_row(const float* __restrict__ logits, c
     if (d_disp) g += d_disp[m] * (-1.f / (ds * ds)) / (1.f / (min_d * sc) - 1.f / (max_d * sc));
     g *= sc;
   } else if (d_disp) g += d_disp[m] * (-inv_rng / (d * d));
-  float o[K];
+  const float gs = g / se;              // softmax_k (bin_k - d) g = e_k (bin_k - d0 - corr) (g / se): one division per pixel
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    float pk = v[k] / se;
     bool inside = raw[k] >= -10.f && raw[k] <= 10.f;  // clamp passes gradient on the closed interval
-    o[k] = inside ? pk * (sb[k] - d) * g : 0.f;
+    o[k] = inside ? (o[k] - v[k] * corr) * gs : 0.f;
   }
 #pragma unroll
   for (int k = 0; k < K; k += 4) store4<T>(dlogits + m * Cl + k, &o[k]);
