@@ -146,6 +146,21 @@ class FsPhotoArgs(C.Structure):
     ]
 
 
+class FsPhotoMultiArgs(C.Structure):
+    _fields_ = [
+        ("img0", C.c_void_p), ("img_src", C.c_void_p * 4), ("patched_mask", C.c_void_p),
+        ("depth", C.c_void_p * 4), ("geo", C.c_void_p),
+        ("pred", C.c_void_p), ("ov", C.c_void_p), ("ident", C.c_void_p), ("sel", C.c_void_p),
+        ("loss_sums", C.c_void_p), ("mask_sum", C.c_void_p),
+        ("d_depth", C.c_void_p * 4), ("dP", C.c_void_p), ("gout", C.c_void_p),
+        ("dh", C.c_int32 * 4), ("dw", C.c_int32 * 4),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("S", C.c_int32),
+        ("nsrc", C.c_int32), ("noise_seed", C.c_int32), ("noise_seed_ptr", C.c_void_p),
+        ("motion_mask", C.c_void_p),
+        ("no_overlap_mask", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
 class FsSmoothArgs(C.Structure):
     _fields_ = [
         ("disp", C.c_void_p * 4), ("color", C.c_void_p * 4), ("d_disp", C.c_void_p * 4),

@@ -6,7 +6,7 @@ import os
 import torch
 
 from .binding import (lib, check, stream_ptr, FsBnApplyArgs, FsBnBwdArgs, FsFlowArgs, FsMotionMaskArgs, FsPhotoArgs,
-                      FsPostOptArgs, FsSmoothArgs)
+                      FsPhotoMultiArgs, FsPostOptArgs, FsSmoothArgs)
 from .conv import dtype_code, _timed, BN_EPS, BN_MOMENTUM, Spec, run_specs
 
 STAT_SLOTS = 8   # FS_STAT_SLOTS in include/fsnet_hip.h
@@ -636,6 +636,159 @@ class PhotometricLoss:
         _timed("photo_fused_bwd", bwd_bytes, lambda: check(lib.fs_photo_fused_bwd(pa, st), "photo_fused_bwd"))
         check(lib.fs_photo_pose_grad(self.geo.data_ptr(), self.dP.data_ptr(), self.dT[0].data_ptr(),
                                      self.dT[1].data_ptr(), self.B, self.S, self.bwd_tiles, st), "photo_pose_grad")
+        if fork is not None:
+            fork[0].wait_stream(fork[1])
+        else:
+            check(lib.fs_smooth_bwd(sa, st), "smooth_bwd")
+        return self.d_depth, self.d_disp, self.dT
+
+
+class PhotometricLossMulti(PhotometricLoss):
+    """The same chain over nsrc = 1..4 temporal source frames, pinhole camera (fs_photo_multi_*).  The accumulators, the
+    smoothness fork, fs_loss_finalize and the prezero registration are PhotometricLoss's; what carries a frame count —
+    geo, ident, pred / ov, dP, dT, the argument struct, the prefetch key and the launches — is overridden here.
+    forward(srcs, Ts) takes nsrc sources and transforms; backward() returns dT as a list of nsrc [B,4,4] views."""
+
+    def __init__(self, B, H, W, scales, device, min_depth, max_depth, nsrc, want_pred=True, overlapped_mask=True):
+        if not 1 <= int(nsrc) <= 4:
+            raise ValueError("PhotometricLossMulti takes 1 to 4 source frames, got %r" % (nsrc,))
+        super().__init__(B, H, W, scales, device, min_depth, max_depth, want_pred=False, overlapped_mask=overlapped_mask)
+        N = self.nsrc = int(nsrc)
+        S = self.S
+        f32, u8 = torch.float32, torch.uint8
+        self.geo = torch.zeros(B, 18 + 12 * N, dtype=f32, device=device)
+        self.want_pred = bool(want_pred)
+        if self.want_pred:
+            self.pred = torch.empty(S, N, B, 3, H, W, dtype=f32, device=device)
+            self.ov = torch.empty(S, N, B, H, W, dtype=u8, device=device)
+        self.ident = torch.empty(B, N, H, W, dtype=f32, device=device)
+        self.bwd_tiles = int(lib.fs_photo_multi_bwd_tiles(H, W))
+        self.dP = torch.zeros(S * B * self.bwd_tiles, N, 12, dtype=f32, device=device)
+        self._dT = torch.zeros(N, B, 4, 4, dtype=f32, device=device)
+        self.dT = [self._dT[f] for f in range(N)]
+        self._pa = FsPhotoMultiArgs()
+        self._Tp = (C.c_void_p * 4)()
+
+    def stage_fisheye(self, tables, mei_rows):
+        raise NotImplementedError("the fisheye loss chain runs two source frames (ops.PhotometricLoss)")
+
+    def _key(self, img0, srcs, patched_mask):
+        return (img0.data_ptr(),) + tuple(s.data_ptr() for s in srcs) + (_p(patched_mask),)
+
+    def _set_inputs(self, img0, srcs, patched_mask):
+        assert len(srcs) == self.nsrc, "expected %d source frames, got %d" % (self.nsrc, len(srcs))
+        pa = self._pa
+        pa.img0 = img0.data_ptr()
+        for f in range(4):
+            pa.img_src[f] = srcs[f].data_ptr() if f < self.nsrc else None
+        pa.patched_mask = _p(patched_mask)
+        pa.ident, pa.mask_sum = self.ident.data_ptr(), self.mask_sum.data_ptr()
+        pa.geo = self.geo.data_ptr()
+        pa.B, pa.H, pa.W, pa.S, pa.nsrc = self.B, self.H, self.W, self.S, self.nsrc
+
+    def prefetch(self, img0, srcs, patched_mask):
+        self._set_inputs(img0, srcs, patched_mask)
+        self._input_only(img0, C.byref(self._pa), stream_ptr())
+        self._prefetched = self._key(img0, srcs, patched_mask)
+
+    def _input_only(self, img0, pa, st):
+        if getattr(self, "_clean_acc", False):
+            _join_pack(img0.device)
+        else:
+            self.acc.zero_()
+        self._clean_acc = False
+        if self._pyr_n:
+            check(lib.fs_color_pyramid_multi(img0.data_ptr(), self._pyr_outs, self._pyr_hs, self._pyr_ws, self._pyr_n,
+                                             self.B, self.H, self.W, st), "color_pyramid_multi")
+        check(lib.fs_photo_multi_identity(pa, st), "photo_multi_identity")
+
+    def _fill(self, img0, srcs, patched_mask, depths, disps, noise_seed, gout):
+        pa, sa = self._pa, self._sa
+        self._set_inputs(img0, srcs, patched_mask)
+        pa.no_overlap_mask = 0 if self.overlapped_mask else 1
+        pa.pred, pa.ov, pa.sel = _p(self.pred), _p(self.ov), self.sel.data_ptr()
+        pa.loss_sums = self.loss_sums.data_ptr()
+        pa.dP = self.dP.data_ptr()
+        pa.gout = _p(gout)
+        pa.noise_seed = -1 if noise_seed is None else int(noise_seed)
+        pa.noise_seed_ptr = self.seed_buf.data_ptr() if noise_seed is None else None
+        pa.motion_mask = _p(self.motion_mask)
+        sa.disp_sum, sa.sm_sums, sa.dot = self.disp_sum.data_ptr(), self.sm_sums.data_ptr(), self.dot.data_ptr()
+        sa.gout = _p(gout)
+        sa.B, sa.S = self.B, self.S
+        for i, (h, w) in enumerate(self.hw):
+            pa.depth[i] = depths[i].data_ptr()
+            pa.dh[i], pa.dw[i] = h, w
+            pa.d_depth[i] = self.d_depth[i].data_ptr()
+            sa.disp[i] = disps[i].data_ptr()
+            sa.color[i] = (img0 if self.scales[i] == 0 else self.pyr[i]).data_ptr()
+            sa.d_disp[i] = self.d_disp[i].data_ptr()
+            sa.h[i], sa.w[i], sa.scale_id[i] = h, w, self.scales[i]
+
+    def forward(self, img0, srcs, P2, Ts, patched_mask, depths, disps, noise_seed=-1, motion_mask=None):
+        """img0, srcs[nsrc]: NCHW fp32; P2 [B,3,4] fp32; Ts[nsrc]: [B,4,4] fp32; the rest as PhotometricLoss.forward"""
+        st = stream_ptr()
+        N = self.nsrc
+        assert len(srcs) == N and len(Ts) == N
+        if motion_mask is not None:
+            assert motion_mask.dtype == torch.float32 and motion_mask.is_contiguous() and motion_mask.shape == (self.B, self.H, self.W)
+        self.motion_mask = motion_mask
+        assert img0.is_contiguous() and all(s.is_contiguous() for s in srcs) and all(T.is_contiguous() for T in Ts)
+        if patched_mask is not None:
+            assert patched_mask.dtype == torch.float64 and patched_mask.is_contiguous()
+        self._keep = (img0, srcs, patched_mask, depths, disps, noise_seed)
+        self._fill(img0, srcs, patched_mask, depths, disps, noise_seed, None)
+        pre, self._prefetched = self._prefetched, None
+        have_inputs = pre == self._key(img0, srcs, patched_mask)
+        pa, sa = C.byref(self._pa), C.byref(self._sa)
+        for f in range(4):
+            self._Tp[f] = Ts[f].data_ptr() if f < N else None
+        check(lib.fs_photo_multi_setup(P2.data_ptr(), self._Tp, N, self.geo.data_ptr(), self.B,
+                                       self.seed_buf.data_ptr() if noise_seed is None else None, st), "photo_multi_setup")
+        if not have_inputs:
+            self._input_only(img0, pa, st)
+        fork = self._fork(img0.device)
+        if fork is not None:          # the smoothness term beside the photometric kernels (PhotometricLoss.forward)
+            fork[1].wait_stream(fork[0])
+            with torch.cuda.stream(fork[1]):
+                st2 = stream_ptr()
+                check(lib.fs_smooth_mean(sa, st2), "smooth_mean")
+                check(lib.fs_smooth_fwd(sa, st2), "smooth_fwd")
+        else:
+            check(lib.fs_smooth_mean(sa, st), "smooth_mean")
+            check(lib.fs_smooth_fwd(sa, st), "smooth_fwd")
+        N_px = float(self.B * self.H * self.W)
+        # algorithmic bytes: per scale, target 12 Npx + nsrc sources 12 nsrc Npx + depth 4 Npx / 4^s + result 4 Npx
+        fwd_bytes = sum(12.0 * (N + 1) * N_px + 4.0 * N_px + 4.0 * N_px / (4 ** s) for s in self.scales)
+        _timed("photo_multi_fwd", fwd_bytes, lambda: check(lib.fs_photo_multi_fwd(pa, st), "photo_multi_fwd"))
+        if fork is not None:
+            fork[0].wait_stream(fork[1])
+        self.out = torch.empty(2 * self.S + 1, dtype=torch.float64, device=img0.device)
+        self.total = torch.empty((), dtype=torch.float64, device=img0.device)
+        check(lib.fs_loss_finalize(self.loss_sums.data_ptr(), self.mask_sum.data_ptr(), self.sm_sums.data_ptr(), sa,
+                                   self.out.data_ptr(), self.total.data_ptr(), st), "loss_finalize")
+        return self.out
+
+    def backward(self, gout=None):
+        st = stream_ptr()
+        img0, srcs, patched_mask, depths, disps, noise_seed = self._keep
+        self._fill(img0, srcs, patched_mask, depths, disps, noise_seed, gout)
+        pa, sa = C.byref(self._pa), C.byref(self._sa)
+        if getattr(self, "_clean_dd", False):
+            _join_pack(img0.device)
+        else:
+            self._dd_flat.zero_()
+        self._clean_dd = False
+        fork = self._fork(img0.device)
+        if fork is not None:
+            fork[1].wait_stream(fork[0])
+            with torch.cuda.stream(fork[1]):
+                check(lib.fs_smooth_bwd(sa, stream_ptr()), "smooth_bwd")
+        N_px = float(self.B * self.H * self.W)
+        bwd_bytes = sum(12.0 * (self.nsrc + 1) * N_px + 4.0 * N_px + 8.0 * N_px / (4 ** s) for s in self.scales)
+        _timed("photo_multi_bwd", bwd_bytes, lambda: check(lib.fs_photo_multi_bwd(pa, st), "photo_multi_bwd"))
+        check(lib.fs_photo_multi_pose_grad(self.geo.data_ptr(), self.dP.data_ptr(), self._dT.data_ptr(), self.nsrc,
+                                           self.B, self.S, self.bwd_tiles, st), "photo_multi_pose_grad")
         if fork is not None:
             fork[0].wait_stream(fork[1])
         else:

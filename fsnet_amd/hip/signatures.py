@@ -98,6 +98,14 @@ SIGNATURES = {
     "fs_photo_fused_bwd": (C.c_int, [P, P]),
     "fs_photo_fused_bwd_tiles": (C.c_int64, [I, I]),
     "fs_photo_pose_grad": (C.c_int, [P, P, P, P, I, I, I, P]),
+    # added under ABI 15: the chain over 1..4 temporal source frames (FsPhotoMultiArgs)
+    "fs_photo_multi_setup": (C.c_int, [P, P, I, P, I, P, P]),
+    "fs_photo_multi_identity": (C.c_int, [P, P]),
+    "fs_photo_multi_fwd": (C.c_int, [P, P]),
+    "fs_photo_multi_bwd": (C.c_int, [P, P]),
+    "fs_photo_multi_bwd_tiles": (C.c_int64, [I, I]),
+    "fs_photo_multi_pose_grad": (C.c_int, [P, P, P, I, I, I, I, P]),
+    "fs_photo_multi_strip": (C.c_int, [I, P, P]),
     "fs_augment_frames": (C.c_int, [P, P]),
     "fs_resize_frames": (C.c_int, [P, P]),
     "fs_augment_frames_masked": (C.c_int, [P, P, P]),

@@ -42,6 +42,38 @@ class _PhotoLossFn(torch.autograd.Function):
         return (None, None, None, None, None, None, None, None, dT[0], dT[1]) + tuple(d_depth) + tuple(d_disp)
 
 
+class _PhotoLossMultiFn(torch.autograd.Function):
+    """_PhotoLossFn over a list of source frames: (pl, S, N, img0, P2, patched_mask, motion_mask, src_1..N, T_1..N,
+    depths, disps); the gradient of the transforms comes back per frame"""
+
+    @staticmethod
+    def forward(ctx, pl, S, N, img0, P2, patched_mask, motion_mask, *rest):
+        ctx.set_materialize_grads(False)
+        srcs = [t.contiguous().float() for t in rest[:N]]
+        Ts = [t.contiguous().float() for t in rest[N:2 * N]]
+        dd = rest[2 * N:]
+        depths = [d.contiguous().float() for d in dd[:S]]
+        disps = [d.contiguous().float() for d in dd[S:]]
+        seed = None if RT.tie_noise else -1
+        RT.mark("photo.fwd.start")
+        out = pl.forward(img0.contiguous().float(), srcs, P2.contiguous().float(), Ts, patched_mask, depths, disps,
+                         noise_seed=seed, motion_mask=None if motion_mask is None else motion_mask.contiguous().float())
+        ctx.pl, ctx.S, ctx.N = pl, S, N
+        ctx.mark_non_differentiable(out)
+        return pl.total, out
+
+    @staticmethod
+    def backward(ctx, g_total, _g_vec):
+        pl, N = ctx.pl, ctx.N
+        gout = None
+        if g_total is not None:
+            gout = g_total.detach().double().contiguous()
+        RT.mark("photo.bwd.start")
+        d_depth, d_disp, dT = pl.backward(gout)
+        RT.mark("photo.bwd.end")
+        return (None,) * 7 + (None,) * N + tuple(dT) + tuple(d_depth) + tuple(d_disp)
+
+
 class _DistillFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, teacher, unc):
@@ -101,8 +133,32 @@ class MonoDepth2Decoder(nn.Module):
             raise NotImplementedError("MonoDepth2Decoder term residualflow_weight > 0 is not implemented in the HIP loss chain")
         if getattr(self, "distillation_loss_weight", 0) > 0 and getattr(self, "is_unscaled_distill", False):
             raise NotImplementedError("is_unscaled_distill=True is not implemented (no shipped config enables it)")
-        if len(self.frame_ids) != 3 or "s" in self.frame_ids:
-            raise NotImplementedError("the HIP loss chain handles frame_ids=[0, a, b] (two temporal source frames)")
+        self._check_frame_ids()
+
+    MAX_SOURCES = 4
+
+    def _check_frame_ids(self):
+        """frame_ids = [0, a, ...]: the target and one to four distinct temporal source frames"""
+        ids = self.frame_ids
+        if "s" in ids:
+            raise NotImplementedError("frame_ids %r: the stereo frame 's' is not implemented in the HIP loss chain "
+                                      "(temporal source frames only)" % (ids,))
+        if len(ids) < 2 or ids[0] != 0 or not all(isinstance(f, int) and not isinstance(f, bool) for f in ids):
+            raise NotImplementedError("frame_ids %r: expected [0, a, ...] with integer frame offsets, the target 0 "
+                                      "first and at least one source frame" % (ids,))
+        if 0 in ids[1:]:
+            raise NotImplementedError("frame_ids %r: a source frame must differ from the target (no 0 after the "
+                                      "first entry)" % (ids,))
+        if len(set(ids)) != len(ids):
+            raise NotImplementedError("frame_ids %r: every source frame may appear once (duplicates)" % (ids,))
+        if len(ids) - 1 > self.MAX_SOURCES:
+            raise NotImplementedError("frame_ids %r: the HIP loss chain takes at most %d source frames, got %d"
+                                      % (ids, self.MAX_SOURCES, len(ids) - 1))
+
+    @property
+    def _two_sources(self):
+        """frame_ids = [0, a, b]: the two-source kernels (photo_fused.hip); every other count runs photo_multi.hip"""
+        return len(self.frame_ids) == 3
 
     def _loss_engine(self, img0):
         B, _, H, W = img0.shape
@@ -112,10 +168,13 @@ class MonoDepth2Decoder(nn.Module):
         key = (B, H, W, tuple(self.scales), device)
         if self._pl is None or self._pl_key != key:
             # the warped images only reach HBM when somebody looks at them (logging; output_dict entries below)
-            self._pl = ops.PhotometricLoss(B, H, W, self.scales, device, self.min_depth, self.max_depth,
-                                           want_pred=bool(getattr(self, "is_log_image", True)
-                                                          or getattr(self, "keep_warped_images", False)),
-                                           overlapped_mask=bool(getattr(self, "overlapped_mask", False)))
+            kw = dict(want_pred=bool(getattr(self, "is_log_image", True) or getattr(self, "keep_warped_images", False)),
+                      overlapped_mask=bool(getattr(self, "overlapped_mask", False)))
+            if self._two_sources:
+                self._pl = ops.PhotometricLoss(B, H, W, self.scales, device, self.min_depth, self.max_depth, **kw)
+            else:
+                self._pl = ops.PhotometricLossMulti(B, H, W, self.scales, device, self.min_depth, self.max_depth,
+                                                    len(self.frame_ids) - 1, **kw)
             self._pl_key = key
         return self._pl
 
@@ -137,13 +196,14 @@ class MonoDepth2Decoder(nn.Module):
     def prefetch_loss_inputs(self, input_dict):
         """launch the input-only part of the loss chain (identity reprojection, colour pyramid) on the current
         stream — the meta-arch calls this on the pose stream, off the depth chain's critical path"""
-        if len(self.frame_ids) != 3 or "s" in self.frame_ids:
-            return
+        try:
+            self._check_frame_ids()
+        except NotImplementedError:
+            return                    # loss() raises it
         img0 = input_dict[("original_image", 0)]
         if not (img0.is_cuda and img0.dtype == torch.float32 and img0.is_contiguous()):
             return
-        fa, fb = self.frame_ids[1], self.frame_ids[2]
-        srcs = [input_dict[("original_image", fa)], input_dict[("original_image", fb)]]
+        srcs = [input_dict[("original_image", f)] for f in self.frame_ids[1:]]
         if not all(s.dtype == torch.float32 and s.is_contiguous() for s in srcs):
             return
         pm = input_dict.get("patched_mask", None)
@@ -163,17 +223,24 @@ class MonoDepth2Decoder(nn.Module):
                 raise NotImplementedError("depth at scale %d must be %dx%d" % (s, H >> s, W >> s))
         self._loss_engine(img0)
         self._stage_geometry(input_dict)
-        fa, fb = self.frame_ids[1], self.frame_ids[2]
+        sources = self.frame_ids[1:]
+        N = len(sources)
         pm = self._mask64(input_dict)
         depths = [output_dict[("depth", s, s)] for s in self.scales]
         disps = [output_dict[("disp", s)] for s in self.scales]
+        Ts = [output_dict[("cam_T_cam", f)] for f in sources]
         # (what the loss differentiates: the training hook's per-chain capture cuts the backward here)
-        self._loss_inputs = ([output_dict[("cam_T_cam", fa)], output_dict[("cam_T_cam", fb)]], depths + disps)
-        total, vec = _PhotoLossFn.apply(self._pl, S, img0, input_dict[("original_image", fa)],
-                                        input_dict[("original_image", fb)], input_dict["P2"], pm,
-                                        input_dict.get("motion_mask", None),
-                                        output_dict[("cam_T_cam", fa)], output_dict[("cam_T_cam", fb)],
-                                        *depths, *disps)
+        self._loss_inputs = (Ts, depths + disps)
+        if self._two_sources:
+            fa, fb = sources
+            total, vec = _PhotoLossFn.apply(self._pl, S, img0, input_dict[("original_image", fa)],
+                                            input_dict[("original_image", fb)], input_dict["P2"], pm,
+                                            input_dict.get("motion_mask", None), Ts[0], Ts[1], *depths, *disps)
+        else:
+            total, vec = _PhotoLossMultiFn.apply(self._pl, S, N, img0, input_dict["P2"], pm,
+                                                 input_dict.get("motion_mask", None),
+                                                 *[input_dict[("original_image", f)] for f in sources], *Ts,
+                                                 *depths, *disps)
         losses = {}
         for k, s in enumerate(self.scales):
             losses["loss/%d" % s] = vec[k]
@@ -183,17 +250,26 @@ class MonoDepth2Decoder(nn.Module):
         # keep_warped_images=True asks for them
         if self._pl.pred is not None:
             for k, s in enumerate(self.scales):
-                for j, f in enumerate((fa, fb)):
+                for j, f in enumerate(sources):
                     output_dict[("original_image", f, s)] = self._pl.pred[k, j]
                     if self._pl.overlapped_mask:      # (the reference only produces it when the option is on)
                         output_dict[("overlapped_mask", f, s)] = self._pl.ov[k, j].view(torch.bool)   # 0/1 bytes
         hm = {}
         if getattr(self, "is_log_image", True) and self._pl.pred is not None:
             hm["original_image"] = img0[0:1]
-            for j, f in enumerate((fa, fb)):
+            for j, f in enumerate(sources):
                 hm["predicted_image_%s" % f] = self._pl.pred[0, j, 0:1]
-            hm["loss_mask_%d" % self.scales[0]] = dict(data=(self._pl.sel[0, 0:1] >= 2).unsqueeze(1))
+            # the reference's literal `idxs >= 2` on its concatenated index (identity 0..N-1, reprojection N..2N-1),
+            # whatever N is: with N = 1 it is never true for a reprojection winner, with N >= 3 it is true for identity
+            # index 2 — the reference's quirk, mirrored.  Its index has no entry for "selected reprojection term whose
+            # sample missed" (2N here): there the constant 100 stands in that term's own slot, >= N
+            hm["loss_mask_%d" % self.scales[0]] = dict(data=self._loss_mask(self._pl.sel[0, 0:1], N).unsqueeze(1))
         return losses, hm, total
+
+    @staticmethod
+    def _loss_mask(sel, N):
+        # sel == 2N stands for a reprojection index in N..2N-1: >= 2 exactly when N >= 2 (N = 1: indices 0 and 1 only)
+        return (sel >= 2) if N >= 2 else torch.zeros_like(sel, dtype=torch.bool)
 
     def compute_pose_loss(self, output_dict, input_dict):
         """sum over the source frames of mean |relative_pose - cam_T_cam| (reference :176-183): the mean-absolute-difference
@@ -242,6 +318,12 @@ class FishEyeDecoder(MonoDepth2Decoder):
         self.mei_projection = MeiCameraProjection()
         self._staged = None          # (P2 tensor, its version, calib list) of the last staging: strong references,
         self._hook_staged = False    # so an equal identity really is the same batch object
+
+    def _check_frame_ids(self):
+        super()._check_frame_ids()
+        if len(self.frame_ids) != 3:
+            raise NotImplementedError("FishEyeDecoder: frame_ids %r — the ray-table (Mei) loss kernels run exactly two "
+                                      "source frames, [0, a, b]" % (self.frame_ids,))
 
     def stage_step_inputs(self, input_dict, from_hook=True):
         """ray tables of this batch's calibrations (built once each, cached by the reference's key) -> the loss

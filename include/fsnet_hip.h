@@ -782,6 +782,55 @@ int64_t fs_photo_fused_bwd_tiles(int H, int W);
 int fs_photo_pose_grad(const float* geo, const float* dP, float* dT0, float* dT1, int B, int S, int tiles,
                        void* stream);
 
+/* The same chain over nsrc = 1..4 temporal source frames, pinhole camera (train_cfg.frame_ids = [0, a, ...]; added under
+ * ABI 15, the two-source entry points above are untouched).  Per frame the arithmetic is that of the two-source kernels;
+ * what changes is the layout:
+ *   geo   [B][18 + 12 nsrc] = invK[9] K[9] P[nsrc][12]
+ *   ident [B][nsrc][H][W]; pred [S][nsrc][B][3][H][W]; ov [S][nsrc][B][H][W]; dP [S][B][tiles][nsrc][12]
+ *   sel   [S][B][H][W]: 0..nsrc-1 identity, nsrc..2 nsrc-1 reprojection, 2 nsrc = a selected reprojection term whose
+ *         sample missed the source frame (the constant 100).  The first of equal candidates wins, in that order.
+ * The tie-break noise is keyed as in fs_photo_fused_fwd with nsrc in place of 2.  Every entry point returns FS_EINVAL
+ * without touching the device for a NULL it needs, nsrc outside 1..4, S outside 1..4, B < 1, H or W < 2 and
+ * 3 H W >= 2^30. */
+typedef struct FsPhotoMultiArgs {
+  const float* img0;
+  const float* img_src[4];      /* the first nsrc are read */
+  const double* patched_mask;   /* [B][H][W] or NULL (= ones) */
+  const float* depth[4];        /* per scale [B][dh][dw] */
+  const float* geo;
+  float* pred;
+  uint8_t* ov;
+  float* ident;
+  uint8_t* sel;
+  double* loss_sums;            /* [S][B] */
+  double* mask_sum;             /* [B] */
+  float* d_depth[4];
+  float* dP;
+  const double* gout;           /* upstream gradient of the total loss (device scalar) or NULL = 1 */
+  int32_t dh[4], dw[4];
+  int32_t B, H, W, S;
+  int32_t nsrc;
+  int32_t noise_seed;
+  const int32_t* noise_seed_ptr;
+  const float* motion_mask;     /* as FsPhotoArgs.motion_mask: the minimum runs over the reprojection terms alone */
+  int32_t no_overlap_mask;
+  int32_t reserved0;
+} FsPhotoMultiArgs;
+/* T: host array of nsrc device pointers [B][4][4]; seed_counter (or NULL) is bumped by one as in fs_photo_setup */
+int fs_photo_multi_setup(const float* P2, const float* const* T, int nsrc, float* geo, int B, int* seed_counter,
+                         void* stream);
+/* the nsrc identity planes (a frame equal to the target gives exactly 0) and mask_sum[b] += sum(patched_mask[b]), once */
+int fs_photo_multi_identity(const FsPhotoMultiArgs* args, void* stream);
+int fs_photo_multi_fwd(const FsPhotoMultiArgs* args, void* stream);
+/* d_depth[s] accumulated (zero it first); dP overwritten, tiles = fs_photo_multi_bwd_tiles(H, W) */
+int fs_photo_multi_bwd(const FsPhotoMultiArgs* args, void* stream);
+int64_t fs_photo_multi_bwd_tiles(int H, int W);
+/* dT[nsrc][B][4][4] = K^T sum_{s,tile} dP in a fixed order */
+int fs_photo_multi_pose_grad(const float* geo, const float* dP, float* dT, int nsrc, int B, int S, int tiles,
+                             void* stream);
+/* output columns and rows of one wave's strip: which = 0 identity, 1 forward, 2 backward */
+int fs_photo_multi_strip(int which, int32_t* cols, int32_t* rows);
+
 /* Mei unified fisheye camera model (mei_fisheye_utils.py:14-187; configs/kitti360_fisheye_example:198-207).
  * fs_mei_lut: the per-calibration table MeiCameraProjection.image2cam caches (:150-166) — for every pixel the radial
  *   distortion is inverted by Newton (newton_methods :70-79) and the mirror equation by bisection (bisection_methods

@@ -164,6 +164,68 @@ def gen_loss_chain():
     np.savez_compressed(os.path.join(GOLD, "loss_chain.npz"), **out)
 
 
+def gen_loss_chain_nsrc():
+    """gen_loss_chain for frame_ids of other lengths: MonoDepth2Decoder.loss of the reference with 1, 3 and 4 temporal
+    source frames at 24 x 56, B = 2 -> inputs, per-scale losses, total, min_idx and the gradients (loss_chain_nsrc.npz)."""
+    B, H, W = 2, 24, 56
+    out = {"H": H, "W": W}
+    for fids in ([0, -1], [0, -2, -1, 1], [0, -2, -1, 1, 2]):
+        N = len(fids) - 1
+        tag = "n%d_" % N
+        data = O.synthetic_batch(B, H, W, seed=30 + N, frame_ids=tuple(fids))
+        data['patched_mask'][:, :3, :] = 0
+        g = torch.Generator().manual_seed(5 + N)
+        dec = ref_model(H, W, False).head
+        dec.frame_ids = list(fids)
+        outputs, leaves = {}, {}
+        for s in range(4):
+            h, w = H >> s, W >> s
+            ys = torch.linspace(0, 1, h).view(1, 1, h, 1)
+            d = (4 + 25 * (1 - ys) + 3 * torch.rand(B, 1, h, w, generator=g)).requires_grad_(True)
+            leaves[("depth", s)] = d
+            outputs[("depth", s, s)] = d
+            outputs[("disp", s)] = mu.depth_to_disp(d, 0.5, 100.0)
+        for f in fids[1:]:
+            aa = (0.01 * torch.randn(B, 1, 3, generator=g)).requires_grad_(True)
+            tr = torch.tensor([[[0.02, -0.01, -0.3 * f]]]).repeat(B, 1, 1) + 0.02 * torch.randn(B, 1, 3, generator=g)
+            tr.requires_grad_(True)
+            leaves[("aa", f)], leaves[("tr", f)] = aa, tr
+            outputs[("cam_T_cam", f)] = mu.transformation_from_parameters(aa, tr, invert=(f < 0))
+        torch.manual_seed(0)
+        res = dec.loss(outputs, data)
+        res['loss'].backward()
+        out[tag + "frame_ids"] = np.asarray(fids, np.int64)
+        out[tag + "total_loss"] = npy(res['loss'])
+        for k, v in res['loss_dict'].items():
+            out[tag + "ld_" + k.replace('/', '_')] = npy(v)
+        # cross-check the oracle, under the same tie-break noise, and take min_idx from it (the reference keeps its index
+        # in a local variable)
+        o2, lv = {}, {}
+        for s in range(4):
+            d = leaves[("depth", s)].detach().clone().requires_grad_(True); lv[s] = d
+            o2[("depth", s, s)] = d; o2[("disp", s)] = O.depth_to_disp(d, 0.5, 100.0)
+        for f in fids[1:]:
+            o2[("cam_T_cam", f)] = outputs[("cam_T_cam", f)].detach()
+        # the reference's tie-break noise (:258-259) is the first draw after torch.manual_seed(0), one per scale
+        torch.manual_seed(0)
+        noise = {s: torch.randn(B, N, H, W) * 0.00001 for s in range(4)}
+        tot, ld = O.photometric_loss(o2, data, frame_ids=tuple(fids), noise=noise)
+        tot.backward()
+        print("oracle chain N=%d: loss dev" % N, dev(tot, res['loss']), "gdepth0 dev rel",
+              dev(lv[0].grad, leaves[("depth", 0)].grad) / float(leaves[("depth", 0)].grad.abs().max()))
+        for s in range(4):
+            out[tag + "depth_%d" % s] = npy(leaves[("depth", s)])
+            out[tag + "gdepth_%d" % s] = npy(leaves[("depth", s)].grad)
+            out[tag + "minidx_%d" % s] = npy(o2[("min_idx", s)]).astype(np.uint8)
+        for f in fids[1:]:
+            out[tag + "aa_%d" % f], out[tag + "tr_%d" % f] = npy(leaves[("aa", f)]), npy(leaves[("tr", f)])
+            out[tag + "gaa_%d" % f], out[tag + "gtr_%d" % f] = npy(leaves[("aa", f)].grad), npy(leaves[("tr", f)].grad)
+        for f in fids:
+            out[tag + "img_%d" % f] = npy(data[("original_image", f)])
+        out[tag + "P2"] = npy(data["P2"]); out[tag + "patched_mask"] = npy(data["patched_mask"])
+    np.savez_compressed(os.path.join(GOLD, "loss_chain_nsrc.npz"), **out)
+
+
 def gen_model(with_pose, tag, steps=3):
     """Full model: forward outputs, loss_dict, per-parameter grad norms, and parameter checksums
     after Adam steps driven by the reference's own BaseTrainingHook (clip 35.0)."""
@@ -1501,6 +1563,9 @@ if __name__ == "__main__":
     if "--only-motion-mask" in sys.argv:
         gen_motion_mask()
         sys.exit(0)
+    if "--only-nsrc" in sys.argv:
+        gen_loss_chain_nsrc()
+        sys.exit(0)
     if "--only-postopt" in sys.argv:
         gen_postopt()
         sys.exit(0)
@@ -1563,6 +1628,7 @@ if __name__ == "__main__":
         sys.exit(0)
     gen_ops()
     gen_loss_chain()
+    gen_loss_chain_nsrc()
     gen_model(True, "depthpose")
     gen_model(False, "wpose")
     gen_eval()
