@@ -51,14 +51,7 @@ struct BRow {
 };
 struct CRow { C3 a, b, c; };                // horizontally box-summed coefficients of one centre row
 
-// FR::count(p): source frames of the launch; FR::split(rest, n, f): take the frame index off the wave number;
-// FR::geo_stride(n): floats of a sample's geo record (invK[9] K[9] P[n][12]).
-struct TwoFrames {
-  template <class A> static __device__ __forceinline__ int count(const A&) { return 2; }
-  static __device__ __forceinline__ void split(int& rest, int, int& f) { f = rest & 1; rest >>= 1; }
-  static __device__ __forceinline__ int geo_stride(int) { return GEO_STRIDE; }
-};
-
+// FR: the frame-count policy (photo_common.h)
 template <bool FISH, class FR, class Args>
 __device__ __forceinline__ void photo_bwd_body(const Args& p, int SX, int SY, int nwaves,
                                                float (*s_dd)[LDS_R * LDS_C]) {

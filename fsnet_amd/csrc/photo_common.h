@@ -1,6 +1,7 @@
-// Device helpers shared by the photometric kernels (photometric.hip: staged kernels; photo_fused.hip: fused ones):
+// Device helpers shared by the photometric kernels (photometric.hip: setup, identity planes, pose gradient;
+// photo_fused.hip / photo_multi.hip: the fused forward and backward over two / one to four source frames):
 // per-pixel geometry (depth upsample -> backproject -> project, pinhole and Mei fisheye), bilinear sampler taps,
-// tie-break noise.  Reference call sites: monodepth2_decoder.py:61-116,355-411; monodepth_utils.py:101-165;
+// tie-break noise, the frame-count policy, the launch helpers.  Reference call sites: monodepth2_decoder.py:61-116,355-411; monodepth_utils.py:101-165;
 // mei_fisheye_utils.py:14-51.
 #pragma once
 #include "common.h"
@@ -12,6 +13,12 @@ namespace {
 constexpr float C1 = 0.01f * 0.01f;
 constexpr float C2 = 0.03f * 0.03f;
 constexpr int GEO_STRIDE = 48;  // per batch element: invK[9] K[9] P[2][12]
+constexpr int MAXF = 4;         // source frames of the N-frame entry points (fs_photo_multi_*)
+__device__ __host__ __forceinline__ int geo_stride_n(int n) { return 18 + 12 * n; }   // invK[9] K[9] P[n][12]
+
+// up to MAXF device pointers as one kernel argument (setup: the transforms; pose gradient: the dT outputs).  Kernels
+// pick an entry with static indices only: a run-time index would copy the table to scratch.
+template <class T> struct PtrTable { T* p[MAXF]; };
 
 __device__ __forceinline__ int refl(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
@@ -161,6 +168,56 @@ __device__ __forceinline__ float tie_noise(int seed, uint32_t key) {
   return 1e-5f * __builtin_amdgcn_sqrtf(-2.f * 0.69314718f * __builtin_amdgcn_logf(u1)) * __builtin_amdgcn_cosf(u2);
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// Frame-count policy: what the two-source kernels (FsPhotoArgs: frame_ids = [0, a, b], pinhole and fisheye) know at
+// compile time and the N-frame ones (FsPhotoMultiArgs: one to four sources, pinhole) read from the launch.  The kernel
+// bodies (photo_fwd_body.h, photo_bwd_body.h, the identity rows of photometric.hip) are one text over it.
+//   count(p)            source frames of the launch
+//   pairs(n)            frame pairs a forward / identity wave walks: the two frames of a pair ride in one f2
+//   full(pr, n)         pair pr holds two frames (a half-filled one, N = 1 or 3, computes its first frame twice)
+//   split(rest, n, f)   take the frame index off a backward wave's number
+//   geo_stride(n)       floats of a sample's geo record
+//   has_ov_mask(p), ov_mask(p, i)   the mask the overlap sample reads: patched_mask, or the fisheye chain's
+//                       patched_mask x ray-table mask (FsPhotoMultiArgs has no such plane)
+// ---------------------------------------------------------------------------------------------
+struct TwoFrames {
+  template <class A> static __device__ __forceinline__ int count(const A&) { return 2; }
+  static __device__ __forceinline__ int pairs(int) { return 1; }
+  static __device__ __forceinline__ bool full(int, int) { return true; }
+  static __device__ __forceinline__ void split(int& rest, int, int& f) { f = rest & 1; rest >>= 1; }
+  static __device__ __forceinline__ int geo_stride(int) { return GEO_STRIDE; }
+  static __device__ __forceinline__ bool has_ov_mask(const FsPhotoArgs& p) { return p.warp_mask || p.patched_mask; }
+  static __device__ __forceinline__ float ov_mask(const FsPhotoArgs& p, long i) {
+    return p.warp_mask ? p.warp_mask[i] : (float)p.patched_mask[i];
+  }
+};
+struct NFrames {
+  static __device__ __forceinline__ int count(const FsPhotoMultiArgs& p) { return p.nsrc; }
+  static __device__ __forceinline__ int pairs(int n) { return (n + 1) >> 1; }
+  static __device__ __forceinline__ bool full(int pr, int n) { return 2 * pr + 1 < n; }
+  static __device__ __forceinline__ void split(int& rest, int n, int& f) { f = rest % n; rest /= n; }
+  static __device__ __forceinline__ int geo_stride(int n) { return geo_stride_n(n); }
+  static __device__ __forceinline__ bool has_ov_mask(const FsPhotoMultiArgs& p) { return p.patched_mask != nullptr; }
+  static __device__ __forceinline__ float ov_mask(const FsPhotoMultiArgs& p, long i) { return (float)p.patched_mask[i]; }
+};
+
+// ---------------------------------------------------------------------------------------------
+// host side of every strip launch
+// ---------------------------------------------------------------------------------------------
+// what every entry point refuses, on either argument struct: a NULL among img0 / geo / the first nsrc sources, S outside
+// 1..4, B < 1, H or W < 2.  (What only some refuse stays with them: 3 H W >= 2^30, the block ceilings, the fisheye pair.)
+template <class Args> inline bool photo_args_ok(const Args* a, int nsrc) {
+  if (!a || !a->img0 || !a->geo) return false;
+  for (int f = 0; f < nsrc; ++f) if (!a->img_src[f]) return false;
+  return a->S >= 1 && a->S <= 4 && a->B >= 1 && a->H >= 2 && a->W >= 2;
+}
+template <class Args> inline bool photo_planes_32bit(const Args* a) { return (long)a->H * a->W * 3 < 0x40000000L; }
+// the ray tables come with their parameters
+inline bool photo_fisheye_ok(const FsPhotoArgs* a) { return (a->lut_ptrs != nullptr) == (a->mei != nullptr); }
+// waves -> blocks of four (256 threads), rounded up to a multiple of `round` (8: whole XCD rounds, for the kernels that
+// re-order their blocks per XCD)
+inline long photo_blocks(long nwaves, int round) { return ((nwaves + 3) / 4 + round - 1) / round * round; }
 }  // namespace
 
 // The helpers below are inlined into kernels of files with different contraction modes, and `#pragma clang fp` is
@@ -177,9 +234,12 @@ __device__ __forceinline__ float tie_noise(int seed, uint32_t key) {
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// row-walking strips (photo_fused.hip, the identity kernel of photometric.hip): lane l of a wave holds column
+// row-walking strips (photo_fwd_body.h, the identity kernel of photometric.hip): lane l of a wave holds column
 // x0 - 1 + l of the strip, lanes 0 and 63 are halo
 // ---------------------------------------------------------------------------------------------
+constexpr int ID_W = 62;              // identity planes: output columns per wave (lanes 1..62)
+constexpr int ID_RS = 16;             // identity planes: output rows per wave (photometric.hip has the measurements)
+
 __device__ __forceinline__ float hsum3(float v) {
   // lane i: v[i-1] + v[i] + v[i+1] (wave-wide shifts; the missing neighbour of lanes 0 / 63 reads 0: halo lanes)
   return (dpp_mov<0x138>(v) + v) + dpp_mov<0x130>(v);

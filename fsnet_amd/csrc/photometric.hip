@@ -9,6 +9,9 @@
 //   compute_total_reprojection_loss (min / masks)     monodepth2_decoder.py:205-292
 // All four scales run in ONE launch per stage (every stage works at full resolution; only the
 // low-res depth map differs).  Images stay planar NCHW fp32 exactly as the data layer hands them over.
+// This file holds what runs unfused: setup, identity planes and pose gradient, one kernel each for the two-source entry
+// points (fs_photo_*) and the N-frame ones (fs_photo_multi_setup / _identity / _pose_grad); the fused forward and
+// backward are photo_fused.hip / photo_multi.hip.
 // FS_HIPCC_FLAGS: -fno-slp-vectorize
 // (as in photo_fused.hip: SLP packing of the row-walking identity kernel's window sums turns each DPP add into a DPP move
 // plus a packed add, costs 12 VGPRs — one wave per SIMD of occupancy — and parks a row's raw values in LDS)
@@ -18,11 +21,11 @@
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// setup: K, K^-1 (f64 adjugate == pinv for a regular K), P_f = (K T_f)[:3]; zero the accumulators
+// setup: K, K^-1 (f64 adjugate == pinv for a regular K), P_f = (K T_f)[:3] for the nsrc frames of a geo record of
+// `stride` floats (fs_photo_setup: 2 frames in 48; fs_photo_multi_setup: 18 + 12 nsrc); bump the noise seed
 // ---------------------------------------------------------------------------------------------
-__global__ void photo_setup_kernel(const float* __restrict__ P2, const float* __restrict__ T0,
-                                   const float* __restrict__ T1, float* __restrict__ geo, int B,
-                                   int* __restrict__ seed_counter, int fisheye) {
+__global__ void photo_setup_kernel(const float* __restrict__ P2, const PtrTable<const float> tp, int nsrc, int stride,
+                                   float* __restrict__ geo, int B, int* __restrict__ seed_counter, int fisheye) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (seed_counter && b == 0) *seed_counter += 1;      // tie-break noise seed of this step (read by the loss forward)
   if (b >= B) return;
@@ -42,14 +45,19 @@ __global__ void photo_setup_kernel(const float* __restrict__ P2, const float* __
   inv[0][2] = (k[0][1] * k[1][2] - k[0][2] * k[1][1]) / det;
   inv[1][2] = (k[0][2] * k[1][0] - k[0][0] * k[1][2]) / det;
   inv[2][2] = (k[0][0] * k[1][1] - k[0][1] * k[1][0]) / det;
-  float* g = geo + (long)b * GEO_STRIDE;
+  float* g = geo + (long)b * stride;
   for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { g[i * 3 + j] = (float)inv[i][j]; g[9 + i * 3 + j] = (float)k[i][j]; }
-  for (int f = 0; f < 2; ++f) {
-    const float* T = (f == 0 ? T0 : T1) + (long)b * 16;
+#pragma unroll
+  for (int f = 0; f < MAXF; ++f) {                     // (unrolled: static indices into the pointer table)
+    if (f >= nsrc) break;
+    // the three rows of T_f and K from registers: the table's pointers carry no __restrict__, so reading either between
+    // the stores to g would be a fresh load per product
+    float T[12];
+    for (int e = 0; e < 12; ++e) T[e] = tp.p[f][(long)b * 16 + e];
     for (int i = 0; i < 3; ++i)
       for (int j = 0; j < 4; ++j) {
         float a = 0.f;
-        for (int m = 0; m < 3; ++m) a += g[9 + i * 3 + m] * T[m * 4 + j];
+        for (int m = 0; m < 3; ++m) a += (float)k[i][m] * T[m * 4 + j];
         g[18 + f * 12 + i * 4 + j] = a;
       }
   }
@@ -169,9 +177,7 @@ __global__ __launch_bounds__(256) void photo_ident_kernel(const FsPhotoArgs p) {
 // 1.5 waves per SIMD of 16 rows hide a row's loads well enough behind the row before it.  (Taken with IEEE quotients;
 // div_nr below then brought 16 rows to 32.7 / 42.6 us.  docs/LAB_r07.md.)
 // ---------------------------------------------------------------------------------------------
-constexpr int ID_W = 62;              // output columns per wave (lanes 1..62)
-constexpr int ID_RS = 16;             // output rows per wave
-
+// (ID_W = 62 columns, ID_RS = 16 rows: photo_common.h)
 // n / d without the scaling steps of the IEEE sequence (ten instructions, a third of the kernel's arithmetic with the
 // six quotients of a pixel): v_rcp_f32 (1 ulp) and one Newton step on the quotient with the exact fma remainder.  Within
 // 1 ulp of n / d, and exactly 1 for n == d (q = 1 + e, the remainder -d e is exact, q - d e r rounds to 1), which the
@@ -184,24 +190,32 @@ __device__ __forceinline__ float div_nr(float n, float d) {
 
 struct IdRow {
   float rt[3];                        // raw target values, per channel
-  f2 rx[3];                           // raw source values (component = source frame)
+  f2 rx[3];                           // raw source values (component = frame of the pair)
   float t[3], tt[3];                  // horizontal 3-tap sums
   f2 x[3], xx[3], xt[3];
 };
 
-__global__ __launch_bounds__(256) void photo_ident_rows_kernel(const FsPhotoArgs p, int SX, int SY, int nwaves) {
+// FR (photo_common.h): TwoFrames = a wave per (sample, strip), both planes; NFrames = a wave per (sample, strip, frame
+// pair), a half-filled pair (N = 1, 3) points its second component at the pair's first frame and drops the copy.  The
+// file is unfused, so the two instantiations give the same bits per plane.
+template <class FR, class Args>
+__global__ __launch_bounds__(256) void photo_ident_rows_kernel(const Args p, int SX, int SY, int nwaves) {
   const int wv = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + ((int)threadIdx.x >> 6));
   if (wv >= nwaves) return;
   const int lane = threadIdx.x & 63;
-  const int sx = wv % SX;
-  const int rest = wv / SX;
+  const int N = FR::count(p), npair = FR::pairs(N);
+  const int pr = wv % npair;
+  int rest = wv / npair;
+  const int sx = rest % SX; rest /= SX;
   const int sy = rest % SY, b = rest / SY;
+  const int fa = 2 * pr;
+  const bool have2 = FR::full(pr, N);
   const int H = p.H, W = p.W;
   const unsigned HW = (unsigned)(H * W);
   const float* timg = p.img0 + (long)b * 3 * HW;
-  const float* src0 = p.img_src[0] + (long)b * 3 * HW;
-  const float* src1 = p.img_src[1] + (long)b * 3 * HW;
-  float* out = p.ident + (long)b * 2 * HW;
+  const float* src0 = p.img_src[fa] + (long)b * 3 * HW;
+  const float* src1 = p.img_src[have2 ? fa + 1 : fa] + (long)b * 3 * HW;
+  float* out = p.ident + ((long)b * N + fa) * HW;
   const double* pm = p.patched_mask ? p.patched_mask + (long)b * HW : nullptr;
   const int x = sx * ID_W - 1 + lane;
   const int xr = min(max(refl(x, W), 0), W - 1);     // (columns past the halo only feed lanes that are not written)
@@ -258,8 +272,8 @@ __global__ __launch_bounds__(256) void photo_ident_rows_kernel(const FsPhotoArgs
       const f2 v = 0.85f * (ssim_sum * k3) + 0.15f * (l1 * k3);
       const unsigned i = (unsigned)(yc * W + x);
       out[i] = v.x;
-      out[HW + i] = v.y;
-      msum += pm ? pm[i] : 1.0;
+      if (have2) out[HW + i] = v.y;
+      if (pr == 0) msum += pm ? pm[i] : 1.0;         // the mask sum is added once, by the first pair's wave
     }
   };
 
@@ -270,25 +284,28 @@ __global__ __launch_bounds__(256) void photo_ident_rows_kernel(const FsPhotoArgs
     if (it + 1 < nsteps) step(C, A, B, it + 1);
     if (it + 2 < nsteps) step(A, B, C, it + 2);
   }
-  msum = wave_sum_d(msum);                           // mask values are 0 / 1: the f64 sum is exact in any order
-  if (lane == 0) atomicAdd(p.mask_sum + b, msum);
+  if (pr == 0) {
+    msum = wave_sum_d(msum);                         // mask values are 0 / 1: the f64 sum is exact in any order
+    if (lane == 0) atomicAdd(p.mask_sum + b, msum);
+  }
 }
 
 // (Rounds 1-2 ran the chain as three staged kernels here — warp to HBM, loss forward, loss backward; the fused kernels of
 // photo_fused.hip replaced them in round 3 and the staged path, kept behind a switch until round 5, is gone.)
 
 // dT[f][b] (4x4, row 3 = 0) = K^T-contracted dP:  P = K3 * T[:3]  =>  dT[k][j] = sum_i K3[i][k] dP[i][j].
-// One block per (b, f): sums the per-tile partials dP[s][b][tile][f][12] of photo_fused_bwd_kernel in a fixed order.
-// A partial is three 16-byte lanes; thread (row lane r of 85, quarter q of 3) strides over the S * tiles rows, the
-// 85 lanes are then added in f64 (first version: 4-byte loads, 366 dependent-latency iterations per thread — 33 us on
-// the critical path between the loss backward and the pose chain's backward).
-__global__ __launch_bounds__(256) void photo_pose_grad_kernel(const float* __restrict__ geo,
-                                                              const float* __restrict__ dP, float* __restrict__ dT0,
-                                                              float* __restrict__ dT1, int B, int S, int tiles) {
+// One block per (b, f) = (blockIdx.x, blockIdx.y): sums the per-tile partials dP[s][b][tile][f of N][12] of the fused
+// backward in a fixed order.  A partial is three 16-byte lanes; thread (row lane r of 85, quarter q of 3) strides over
+// the S * tiles rows, the 85 lanes are then added in f64 (first version: 4-byte loads, 366 dependent-latency iterations
+// per thread — 33 us on the critical path between the loss backward and the pose chain's backward).
+// dT: one [B][4][4] output per frame (fs_photo_pose_grad: two tensors; fs_photo_multi_pose_grad: slices of one).
+__global__ __launch_bounds__(256) void photo_pose_grad_kernel(const float* __restrict__ geo, int stride,
+                                                              const float* __restrict__ dP, const PtrTable<float> dT,
+                                                              int N, int B, int S, int tiles) {
   constexpr int RL = 85;
   __shared__ double s_part[RL][12];
   __shared__ float s_g[12];
-  const int b = blockIdx.x >> 1, f = blockIdx.x & 1;
+  const int b = blockIdx.x, f = blockIdx.y;
   const int t = threadIdx.x, q = t % 3, r = t / 3;
   if (r < RL) {
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
@@ -296,7 +313,7 @@ __global__ __launch_bounds__(256) void photo_pose_grad_kernel(const float* __res
 #pragma unroll 4
     for (int j = r; j < rows; j += RL) {
       const int s = j / tiles, tl = j - s * tiles;
-      const float4 v = *reinterpret_cast<const float4*>(dP + ((((long)s * B + b) * tiles + tl) * 2 + f) * 12 + q * 4);
+      const float4 v = *reinterpret_cast<const float4*>(dP + ((((long)s * B + b) * tiles + tl) * N + f) * 12 + q * 4);
       a0 += (double)v.x; a1 += (double)v.y; a2 += (double)v.z; a3 += (double)v.w;
     }
     s_part[r][q * 4 + 0] = a0; s_part[r][q * 4 + 1] = a1; s_part[r][q * 4 + 2] = a2; s_part[r][q * 4 + 3] = a3;
@@ -309,18 +326,27 @@ __global__ __launch_bounds__(256) void photo_pose_grad_kernel(const float* __res
   }
   __syncthreads();
   if (t < 16) {
-    const float* K = geo + (long)b * GEO_STRIDE + 9;
-    float* o = (f == 0 ? dT0 : dT1) + (long)b * 16;
+    const float* K = geo + (long)b * stride + 9;
+    float* o = (f == 0 ? dT.p[0] : f == 1 ? dT.p[1] : f == 2 ? dT.p[2] : dT.p[3]) + (long)b * 16;
     const int rr = t >> 2, j = t & 3;
     o[t] = rr < 3 ? K[0 * 3 + rr] * s_g[0 * 4 + j] + K[1 * 3 + rr] * s_g[1 * 4 + j] + K[2 * 3 + rr] * s_g[2 * 4 + j] : 0.f;
   }
 }
 
-bool valid(const FsPhotoArgs* a) {
-  if (!a || !a->img0 || !a->img_src[0] || !a->img_src[1] || !a->geo) return false;
-  if (a->S < 1 || a->S > 4 || a->B < 1 || a->H < 2 || a->W < 2) return false;
-  if ((a->lut_ptrs != nullptr) != (a->mei != nullptr)) return false;   // the ray tables come with their parameters
-  return true;
+// the identity launch of either argument struct: a wave per (sample, strip, frame pair), four waves a block
+template <class FR, class Args> int launch_ident_rows(const Args* a, int npair, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int SX = (a->W + ID_W - 1) / ID_W, SY = (a->H + ID_RS - 1) / ID_RS;
+  const long nwaves = (long)a->B * SY * SX * npair;
+  if (nwaves > 0x7ffffff0L) return FS_EINVAL;
+  hipLaunchKernelGGL((photo_ident_rows_kernel<FR, Args>), dim3((unsigned)photo_blocks(nwaves, 1)), dim3(256), 0, st, *a,
+                     SX, SY, (int)nwaves);
+  return fs_launch_status();
+}
+
+bool valid(const FsPhotoArgs* a) { return photo_args_ok(a, 2) && photo_fisheye_ok(a); }
+bool valid(const FsPhotoMultiArgs* a) {
+  return a && a->nsrc >= 1 && a->nsrc <= MAXF && photo_args_ok(a, a->nsrc) && photo_planes_32bit(a);
 }
 
 }  // namespace
@@ -329,8 +355,23 @@ extern "C" int fs_photo_setup(const float* P2, const float* T0, const float* T1,
                               int fisheye, void* stream) {
   if (!P2 || !T0 || !T1 || !geo) return FS_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(photo_setup_kernel, dim3((B + 63) / 64), dim3(64), 0, st, P2, T0, T1, geo, B, seed_counter,
-                     fisheye);
+  const PtrTable<const float> tp = {{T0, T1}};
+  hipLaunchKernelGGL(photo_setup_kernel, dim3((B + 63) / 64), dim3(64), 0, st, P2, tp, 2, GEO_STRIDE, geo, B,
+                     seed_counter, fisheye);
+  return fs_launch_status();
+}
+
+extern "C" int fs_photo_multi_setup(const float* P2, const float* const* T, int nsrc, float* geo, int B,
+                                    int* seed_counter, void* stream) {
+  if (!P2 || !T || !geo || nsrc < 1 || nsrc > MAXF || B < 1) return FS_EINVAL;
+  PtrTable<const float> tp = {};
+  for (int f = 0; f < nsrc; ++f) {
+    if (!T[f]) return FS_EINVAL;
+    tp.p[f] = T[f];
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(photo_setup_kernel, dim3((B + 63) / 64), dim3(64), 0, st, P2, tp, nsrc, geo_stride_n(nsrc), geo, B,
+                     seed_counter, 0);
   return fs_launch_status();
 }
 
@@ -343,15 +384,13 @@ extern "C" int fs_photo_identity(const FsPhotoArgs* a, void* stream) {
 }
 
 extern "C" int fs_photo_identity_rows(const FsPhotoArgs* a, void* stream) {
+  if (!valid(a) || !a->ident || !a->mask_sum || !photo_planes_32bit(a)) return FS_EINVAL;
+  return launch_ident_rows<TwoFrames>(a, 1, stream);
+}
+
+extern "C" int fs_photo_multi_identity(const FsPhotoMultiArgs* a, void* stream) {
   if (!valid(a) || !a->ident || !a->mask_sum) return FS_EINVAL;
-  if ((long)a->H * a->W * 3 >= 0x40000000L) return FS_EINVAL;          // 32-bit plane offsets
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int SX = (a->W + ID_W - 1) / ID_W, SY = (a->H + ID_RS - 1) / ID_RS;
-  const long nwaves = (long)a->B * SY * SX;
-  const long nblk = (nwaves + 3) / 4;
-  if (nwaves > 0x7ffffff0L) return FS_EINVAL;
-  hipLaunchKernelGGL(photo_ident_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, st, *a, SX, SY, (int)nwaves);
-  return fs_launch_status();
+  return launch_ident_rows<NFrames>(a, (a->nsrc + 1) / 2, stream);
 }
 
 extern "C" int fs_photo_identity_strip_rows(void) { return ID_RS; }
@@ -360,6 +399,18 @@ extern "C" int fs_photo_pose_grad(const float* geo, const float* dP, float* dT0,
                                   void* stream) {
   if (!geo || !dP || !dT0 || !dT1 || B < 1 || S < 1 || tiles < 1) return FS_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(photo_pose_grad_kernel, dim3(2 * B), dim3(256), 0, st, geo, dP, dT0, dT1, B, S, tiles);
+  const PtrTable<float> dT = {{dT0, dT1}};
+  hipLaunchKernelGGL(photo_pose_grad_kernel, dim3(B, 2), dim3(256), 0, st, geo, GEO_STRIDE, dP, dT, 2, B, S, tiles);
+  return fs_launch_status();
+}
+
+extern "C" int fs_photo_multi_pose_grad(const float* geo, const float* dP, float* dT, int nsrc, int B, int S, int tiles,
+                                        void* stream) {
+  if (!geo || !dP || !dT || nsrc < 1 || nsrc > MAXF || B < 1 || S < 1 || S > 4 || tiles < 1) return FS_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  PtrTable<float> t = {};
+  for (int f = 0; f < nsrc; ++f) t.p[f] = dT + (long)f * B * 16;
+  hipLaunchKernelGGL(photo_pose_grad_kernel, dim3(B, nsrc), dim3(256), 0, st, geo, geo_stride_n(nsrc), dP, t, nsrc, B, S,
+                     tiles);
   return fs_launch_status();
 }

@@ -408,13 +408,54 @@ def pose_tail_bwd(x, dT, nframes, invert, dtype, scale=0.01, out=None):
     return dx
 
 
+class _PhotoBackend:
+    """What differs between the two sets of loss kernels: the argument struct, the launches and the names the profile
+    tools key on.  setup(pl, P2, Ts, seed, st) and pose_grad(pl, st) take the engine; the rest take (args, stream)."""
+
+    def __init__(self, name, args, geo_floats, setup, identity, fwd, bwd, pose_grad, bwd_tiles):
+        self.name, self.args, self.geo_floats = name, args, geo_floats
+        self.setup, self.identity, self.fwd, self.bwd, self.pose_grad, self.bwd_tiles = setup, identity, fwd, bwd, pose_grad, bwd_tiles
+
+
+def _photo_backend(multi):
+    if not multi:        # frame_ids = [0, a, b], pinhole and fisheye: fs_photo_*
+        return _PhotoBackend(
+            "photo_fused", FsPhotoArgs, lambda n: 48,
+            lambda pl, P2, Ts, seed, st: lib.fs_photo_setup(P2.data_ptr(), Ts[0].data_ptr(), Ts[1].data_ptr(),
+                                                            pl.geo.data_ptr(), pl.B, seed, int(pl.fisheye), st),
+            lib.fs_photo_identity_rows, lib.fs_photo_fused_fwd, lib.fs_photo_fused_bwd,
+            lambda pl, st: lib.fs_photo_pose_grad(pl.geo.data_ptr(), pl.dP.data_ptr(), pl.dT[0].data_ptr(),
+                                                  pl.dT[1].data_ptr(), pl.B, pl.S, pl.bwd_tiles, st),
+            lib.fs_photo_fused_bwd_tiles)
+
+    def setup(pl, P2, Ts, seed, st):
+        for f in range(4):
+            pl._Tp[f] = Ts[f].data_ptr() if f < pl.nsrc else None
+        return lib.fs_photo_multi_setup(P2.data_ptr(), pl._Tp, pl.nsrc, pl.geo.data_ptr(), pl.B, seed, st)
+
+    return _PhotoBackend(      # one to four sources, pinhole: fs_photo_multi_*
+        "photo_multi", FsPhotoMultiArgs, lambda n: 18 + 12 * n, setup,
+        lib.fs_photo_multi_identity, lib.fs_photo_multi_fwd, lib.fs_photo_multi_bwd,
+        lambda pl, st: lib.fs_photo_multi_pose_grad(pl.geo.data_ptr(), pl.dP.data_ptr(), pl._dT.data_ptr(), pl.nsrc, pl.B,
+                                                    pl.S, pl.bwd_tiles, st),
+        lib.fs_photo_multi_bwd_tiles)
+
+
 class PhotometricLoss:
-    """Fused loss chain for one batch geometry (B, H, W, scales).  forward() returns the loss
-    vector (f64 [2S+1]: loss/s, smooth_loss/s, total); backward() returns d depth_s and dT_f.
+    """Fused loss chain for one batch geometry (B, H, W, scales) over nsrc = 1..4 source frames.  forward() returns the
+    loss vector (f64 [2S+1]: loss/s, smooth_loss/s, total); backward() returns d depth_s and dT_f (nsrc [B,4,4] views).
+    nsrc == 2 runs the two-source kernels (fs_photo_*; the only ones with the fisheye model), every other count the
+    N-frame ones (fs_photo_multi_*); force_multi=True puts nsrc == 2 on those as well (their tests).
     want_pred: also materialise the warped images / overlap masks (self.pred, self.ov) — only needed for logging and
     for the ("original_image", f, s) entries the reference leaves in its output dict."""
 
-    def __init__(self, B, H, W, scales, device, min_depth, max_depth, want_pred=True, overlapped_mask=True):
+    def __init__(self, B, H, W, scales, device, min_depth, max_depth, want_pred=True, overlapped_mask=True, nsrc=2,
+                 force_multi=False):
+        if not 1 <= int(nsrc) <= 4:
+            raise ValueError("PhotometricLoss takes 1 to 4 source frames, got %r" % (nsrc,))
+        N = self.nsrc = int(nsrc)
+        self.multi = bool(force_multi) or N != 2
+        be = self._be = _photo_backend(self.multi)
         self.B, self.H, self.W = B, H, W
         # overlapped_mask=False (multi_dataset / nusc configs): reprojection terms are used wherever they are, with
         # border-clamped samples (monodepth2_decoder.py:110-116, 230-235)
@@ -423,13 +464,13 @@ class PhotometricLoss:
         S = self.S = len(self.scales)
         self.device = device
         f32, f64, u8 = torch.float32, torch.float64, torch.uint8
-        self.geo = torch.zeros(B, 48, dtype=f32, device=device)
+        self.geo = torch.zeros(B, be.geo_floats(N), dtype=f32, device=device)
         self.want_pred = bool(want_pred)
         self.pred = self.ov = None
         if self.want_pred:
-            self.pred = torch.empty(S, 2, B, 3, H, W, dtype=f32, device=device)
-            self.ov = torch.empty(S, 2, B, H, W, dtype=u8, device=device)
-        self.ident = torch.empty(B, 2, H, W, dtype=f32, device=device)
+            self.pred = torch.empty(S, N, B, 3, H, W, dtype=f32, device=device)
+            self.ov = torch.empty(S, N, B, H, W, dtype=u8, device=device)
+        self.ident = torch.empty(B, N, H, W, dtype=f32, device=device)
         self.sel = torch.empty(S, B, H, W, dtype=u8, device=device)
         # accumulators zeroed every step in one memset: loss_sums[S*B] mask_sum[B] disp_sum[S*B] sm_sums[2*S*B] dot[S*B]
         self.n_acc = S * B + B + S * B + 2 * S * B + S * B
@@ -443,8 +484,8 @@ class PhotometricLoss:
         self.out = torch.zeros(2 * S + 1, dtype=f64, device=device)
         self.hw = [(H >> s, W >> s) for s in self.scales]
         self.color = [None] * S
-        self.bwd_tiles = int(lib.fs_photo_fused_bwd_tiles(H, W))
-        self.dP = torch.zeros(self.S * B * self.bwd_tiles, 2, 12, dtype=f32, device=device)   # per-tile partials
+        self.bwd_tiles = int(be.bwd_tiles(H, W))
+        self.dP = torch.zeros(self.S * B * self.bwd_tiles, N, 12, dtype=f32, device=device)   # per-tile partials
         # one flat buffer behind the per-scale depth gradients: a single memset per backward instead of one per scale
         sizes = [B * h * w for (h, w) in self.hw]
         self._dd_flat = torch.zeros(sum(sizes), dtype=f32, device=device)
@@ -453,7 +494,8 @@ class PhotometricLoss:
             self.d_depth.append(self._dd_flat[o:o + n_el].view(B, 1, h, w))
             o += n_el
         self.d_disp = [torch.empty(B, 1, h, w, dtype=f32, device=device) for (h, w) in self.hw]
-        self.dT = [torch.zeros(B, 4, 4, dtype=f32, device=device) for _ in range(2)]
+        self._dT = torch.zeros(N, B, 4, 4, dtype=f32, device=device)
+        self.dT = [self._dT[f] for f in range(N)]
         self.pyr = [None if s == 0 else torch.empty(B, 3, H >> s, W >> s, dtype=f32, device=device)
                     for s in self.scales]
         # the levels below full resolution as host arrays for fs_color_pyramid_multi (the buffers are persistent)
@@ -462,7 +504,8 @@ class PhotometricLoss:
         self._pyr_outs = (C.c_void_p * max(len(lv), 1))(*[self.pyr[i].data_ptr() for i in lv])
         self._pyr_hs = (C.c_int32 * max(len(lv), 1))(*[self.hw[i][0] for i in lv])
         self._pyr_ws = (C.c_int32 * max(len(lv), 1))(*[self.hw[i][1] for i in lv])
-        self._pa = FsPhotoArgs()
+        self._pa = be.args()
+        self._Tp = (C.c_void_p * 4)()
         self._sa = FsSmoothArgs()
         self.seed_buf = torch.zeros(1, dtype=torch.int32, device=device)   # device-resident tie-break seed
         self._prefetched = None
@@ -478,6 +521,8 @@ class PhotometricLoss:
     def stage_fisheye(self, tables, mei_rows):
         """tables: B device tensors [4,H,W] (fs_mei_lut); mei_rows: host float32 [B,8] = k1 k2 xi g1 g2 u0 v0 0.
         Copies the pointer table and the parameters into persistent device buffers on the current stream."""
+        if self.multi:
+            raise NotImplementedError("the fisheye loss chain runs two source frames (ops.PhotometricLoss)")
         B, dev = self.B, self.device
         if self.lut_table is None:
             self.lut_table = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -495,19 +540,29 @@ class PhotometricLoss:
         self._lut_keep = (list(tables), ptrs, mei_rows.copy())
         self.fisheye = True
 
-    def prefetch(self, img0, srcs, patched_mask):
-        """The part of the chain that only needs the batch (accumulator reset, colour pyramid, identity
-        reprojection + mask sum): may run on another stream beside the networks; forward() then skips it."""
-        st = stream_ptr()
+    @staticmethod
+    def _key(img0, srcs, patched_mask):
+        return (img0.data_ptr(),) + tuple(s.data_ptr() for s in srcs) + (_p(patched_mask),)
+
+    def _set_inputs(self, img0, srcs, patched_mask):
+        assert len(srcs) == self.nsrc, "expected %d source frames, got %d" % (self.nsrc, len(srcs))
         pa = self._pa
         pa.img0 = img0.data_ptr()
-        pa.img_src[0], pa.img_src[1] = srcs[0].data_ptr(), srcs[1].data_ptr()
+        for f in range(len(pa.img_src)):
+            pa.img_src[f] = srcs[f].data_ptr() if f < self.nsrc else None
         pa.patched_mask = _p(patched_mask)
         pa.ident, pa.mask_sum = self.ident.data_ptr(), self.mask_sum.data_ptr()
         pa.geo = self.geo.data_ptr()
         pa.B, pa.H, pa.W, pa.S = self.B, self.H, self.W, self.S
-        self._input_only(img0, C.byref(pa), st)
-        self._prefetched = (img0.data_ptr(), srcs[0].data_ptr(), srcs[1].data_ptr(), _p(patched_mask))
+        if self.multi:
+            pa.nsrc = self.nsrc
+
+    def prefetch(self, img0, srcs, patched_mask):
+        """The part of the chain that only needs the batch (accumulator reset, colour pyramid, identity
+        reprojection + mask sum): may run on another stream beside the networks; forward() then skips it."""
+        self._set_inputs(img0, srcs, patched_mask)
+        self._input_only(img0, C.byref(self._pa), stream_ptr())
+        self._prefetched = self._key(img0, srcs, patched_mask)
 
     def _prezero(self):
         """(ops.prezero_all) the accumulators and the depth-gradient maps are about to be zeroed at the step's head"""
@@ -523,26 +578,23 @@ class PhotometricLoss:
         if self._pyr_n:
             check(lib.fs_color_pyramid_multi(img0.data_ptr(), self._pyr_outs, self._pyr_hs, self._pyr_ws, self._pyr_n,
                                              self.B, self.H, self.W, st), "color_pyramid_multi")
-        check(lib.fs_photo_identity_rows(pa, st), "photo_identity_rows")
+        check(self._be.identity(pa, st), "photo_multi_identity" if self.multi else "photo_identity_rows")
 
     def _fill(self, img0, srcs, patched_mask, depths, disps, noise_seed, gout):
         pa, sa = self._pa, self._sa
-        pa.img0 = img0.data_ptr()
-        pa.img_src[0], pa.img_src[1] = srcs[0].data_ptr(), srcs[1].data_ptr()
-        pa.patched_mask = _p(patched_mask)
-        pa.geo = self.geo.data_ptr()
+        self._set_inputs(img0, srcs, patched_mask)
         pa.no_overlap_mask = 0 if self.overlapped_mask else 1
-        pa.pred, pa.ov, pa.ident, pa.sel = _p(self.pred), _p(self.ov), self.ident.data_ptr(), self.sel.data_ptr()
-        pa.loss_sums, pa.mask_sum = self.loss_sums.data_ptr(), self.mask_sum.data_ptr()
+        pa.pred, pa.ov, pa.sel = _p(self.pred), _p(self.ov), self.sel.data_ptr()
+        pa.loss_sums = self.loss_sums.data_ptr()
         pa.dP = self.dP.data_ptr()
         pa.gout = _p(gout)
-        pa.B, pa.H, pa.W, pa.S = self.B, self.H, self.W, self.S
         pa.noise_seed = -1 if noise_seed is None else int(noise_seed)
         pa.noise_seed_ptr = self.seed_buf.data_ptr() if noise_seed is None else None
-        if self.fisheye:
-            pa.lut_ptrs, pa.mei, pa.warp_mask = self.lut_table.data_ptr(), self.mei.data_ptr(), self.warp_mask.data_ptr()
-        else:
-            pa.lut_ptrs = pa.mei = pa.warp_mask = None
+        if not self.multi:
+            if self.fisheye:
+                pa.lut_ptrs, pa.mei, pa.warp_mask = self.lut_table.data_ptr(), self.mei.data_ptr(), self.warp_mask.data_ptr()
+            else:
+                pa.lut_ptrs = pa.mei = pa.warp_mask = None
         pa.motion_mask = _p(self.motion_mask)
         sa.disp_sum, sa.sm_sums, sa.dot = self.disp_sum.data_ptr(), self.sm_sums.data_ptr(), self.dot.data_ptr()
         sa.gout = _p(gout)
@@ -556,25 +608,32 @@ class PhotometricLoss:
             sa.d_disp[i] = self.d_disp[i].data_ptr()
             sa.h[i], sa.w[i], sa.scale_id[i] = h, w, self.scales[i]
 
+    def _bytes(self, depth_passes):
+        """algorithmic bytes of the fused forward (depth read once) / backward (depth read + gradient written) (SURVEY
+        §8d): per scale, target 12 Npx + nsrc sources 12 nsrc Npx + depth 4 Npx / 4^s per pass + result 4 Npx"""
+        N_px = float(self.B * self.H * self.W)
+        return sum(12.0 * (self.nsrc + 1) * N_px + 4.0 * N_px + 4.0 * depth_passes * N_px / (4 ** s) for s in self.scales)
+
     def forward(self, img0, srcs, P2, Ts, patched_mask, depths, disps, noise_seed=-1, motion_mask=None):
-        """img0, srcs[2]: NCHW fp32; P2 [B,3,4] fp32; Ts[2]: [B,4,4] fp32; patched_mask f64 [B,H,W] or None;
+        """img0, srcs[nsrc]: NCHW fp32; P2 [B,3,4] fp32; Ts[nsrc]: [B,4,4] fp32; patched_mask f64 [B,H,W] or None;
         depths/disps: per scale [B,1,h,w] fp32 contiguous; motion_mask: fp32 [B,H,W] or None."""
         st = stream_ptr()
+        be = self._be
+        assert len(srcs) == self.nsrc and len(Ts) == self.nsrc
         if motion_mask is not None:
             assert motion_mask.dtype == torch.float32 and motion_mask.is_contiguous() and motion_mask.shape == (self.B, self.H, self.W)
         self.motion_mask = motion_mask
-        assert img0.is_contiguous() and all(s.is_contiguous() for s in srcs)
+        assert img0.is_contiguous() and all(s.is_contiguous() for s in srcs) and all(T.is_contiguous() for T in Ts)
         if patched_mask is not None:
             assert patched_mask.dtype == torch.float64 and patched_mask.is_contiguous()
         self._keep = (img0, srcs, patched_mask, depths, disps, noise_seed)
         self._fill(img0, srcs, patched_mask, depths, disps, noise_seed, None)
         pre, self._prefetched = self._prefetched, None
-        have_inputs = pre == (img0.data_ptr(), srcs[0].data_ptr(), srcs[1].data_ptr(), _p(patched_mask))
+        have_inputs = pre == self._key(img0, srcs, patched_mask)
         pa, sa = C.byref(self._pa), C.byref(self._sa)
         # (noise_seed None: the setup kernel bumps the device seed — fresh noise every step, also on a graph replay)
-        check(lib.fs_photo_setup(P2.data_ptr(), Ts[0].data_ptr(), Ts[1].data_ptr(), self.geo.data_ptr(), self.B,
-                                 self.seed_buf.data_ptr() if noise_seed is None else None, int(self.fisheye), st),
-              "photo_setup")
+        check(be.setup(self, P2, Ts, self.seed_buf.data_ptr() if noise_seed is None else None, st),
+              "photo_multi_setup" if self.multi else "photo_setup")
         if self.fisheye:
             check(lib.fs_mei_stage_mask(self.lut_table.data_ptr(), _p(patched_mask), self.warp_mask.data_ptr(), self.B,
                                         self.H, self.W, st), "mei_stage_mask")
@@ -592,10 +651,7 @@ class PhotometricLoss:
         else:
             check(lib.fs_smooth_mean(sa, st), "smooth_mean")
             check(lib.fs_smooth_fwd(sa, st), "smooth_fwd")
-        N_px = float(self.B * self.H * self.W)
-        # algorithmic bytes: per scale, target 12N + 2 sources 24N + depth 4N/4^s + result 4N
-        fwd_bytes = sum(40.0 * N_px + 4.0 * N_px / (4 ** s) for s in self.scales)
-        _timed("photo_fused_fwd", fwd_bytes, lambda: check(lib.fs_photo_fused_fwd(pa, st), "photo_fused_fwd"))
+        _timed(be.name + "_fwd", self._bytes(1), lambda: check(be.fwd(pa, st), be.name + "_fwd"))
         if fork is not None:
             fork[0].wait_stream(fork[1])         # smoothness sums (side stream) before the finalize kernel
         # fresh result tensors per call (the previous step's stay valid for whoever kept them) — the kernel writes
@@ -618,6 +674,7 @@ class PhotometricLoss:
     def backward(self, gout=None):
         """gout: device f64 scalar (upstream grad of total loss) or None (=1)."""
         st = stream_ptr()
+        be = self._be
         img0, srcs, patched_mask, depths, disps, noise_seed = self._keep
         self._fill(img0, srcs, patched_mask, depths, disps, noise_seed, gout)
         pa, sa = C.byref(self._pa), C.byref(self._sa)
@@ -631,11 +688,8 @@ class PhotometricLoss:
             fork[1].wait_stream(fork[0])
             with torch.cuda.stream(fork[1]):
                 check(lib.fs_smooth_bwd(sa, stream_ptr()), "smooth_bwd")
-        N_px = float(self.B * self.H * self.W)
-        bwd_bytes = sum(40.0 * N_px + 8.0 * N_px / (4 ** s) for s in self.scales)
-        _timed("photo_fused_bwd", bwd_bytes, lambda: check(lib.fs_photo_fused_bwd(pa, st), "photo_fused_bwd"))
-        check(lib.fs_photo_pose_grad(self.geo.data_ptr(), self.dP.data_ptr(), self.dT[0].data_ptr(),
-                                     self.dT[1].data_ptr(), self.B, self.S, self.bwd_tiles, st), "photo_pose_grad")
+        _timed(be.name + "_bwd", self._bytes(2), lambda: check(be.bwd(pa, st), be.name + "_bwd"))
+        check(be.pose_grad(self, st), "photo_multi_pose_grad" if self.multi else "photo_pose_grad")
         if fork is not None:
             fork[0].wait_stream(fork[1])
         else:
@@ -643,157 +697,19 @@ class PhotometricLoss:
         return self.d_depth, self.d_disp, self.dT
 
 
-class PhotometricLossMulti(PhotometricLoss):
-    """The same chain over nsrc = 1..4 temporal source frames, pinhole camera (fs_photo_multi_*).  The accumulators, the
-    smoothness fork, fs_loss_finalize and the prezero registration are PhotometricLoss's; what carries a frame count —
-    geo, ident, pred / ov, dP, dT, the argument struct, the prefetch key and the launches — is overridden here.
-    forward(srcs, Ts) takes nsrc sources and transforms; backward() returns dT as a list of nsrc [B,4,4] views."""
+class _OnMultiBackend(type):
+    def __instancecheck__(cls, obj):
+        return isinstance(obj, PhotometricLoss) and obj.multi
+
+
+class PhotometricLossMulti(PhotometricLoss, metaclass=_OnMultiBackend):
+    """The earlier name of PhotometricLoss(..., nsrc=nsrc, force_multi=True), with nsrc in its old position.  No code
+    of its own: the name is kept for callers written against it, and isinstance() answers whether an engine — built
+    under either name — runs the N-frame kernels."""
 
     def __init__(self, B, H, W, scales, device, min_depth, max_depth, nsrc, want_pred=True, overlapped_mask=True):
-        if not 1 <= int(nsrc) <= 4:
-            raise ValueError("PhotometricLossMulti takes 1 to 4 source frames, got %r" % (nsrc,))
-        super().__init__(B, H, W, scales, device, min_depth, max_depth, want_pred=False, overlapped_mask=overlapped_mask)
-        N = self.nsrc = int(nsrc)
-        S = self.S
-        f32, u8 = torch.float32, torch.uint8
-        self.geo = torch.zeros(B, 18 + 12 * N, dtype=f32, device=device)
-        self.want_pred = bool(want_pred)
-        if self.want_pred:
-            self.pred = torch.empty(S, N, B, 3, H, W, dtype=f32, device=device)
-            self.ov = torch.empty(S, N, B, H, W, dtype=u8, device=device)
-        self.ident = torch.empty(B, N, H, W, dtype=f32, device=device)
-        self.bwd_tiles = int(lib.fs_photo_multi_bwd_tiles(H, W))
-        self.dP = torch.zeros(S * B * self.bwd_tiles, N, 12, dtype=f32, device=device)
-        self._dT = torch.zeros(N, B, 4, 4, dtype=f32, device=device)
-        self.dT = [self._dT[f] for f in range(N)]
-        self._pa = FsPhotoMultiArgs()
-        self._Tp = (C.c_void_p * 4)()
-
-    def stage_fisheye(self, tables, mei_rows):
-        raise NotImplementedError("the fisheye loss chain runs two source frames (ops.PhotometricLoss)")
-
-    def _key(self, img0, srcs, patched_mask):
-        return (img0.data_ptr(),) + tuple(s.data_ptr() for s in srcs) + (_p(patched_mask),)
-
-    def _set_inputs(self, img0, srcs, patched_mask):
-        assert len(srcs) == self.nsrc, "expected %d source frames, got %d" % (self.nsrc, len(srcs))
-        pa = self._pa
-        pa.img0 = img0.data_ptr()
-        for f in range(4):
-            pa.img_src[f] = srcs[f].data_ptr() if f < self.nsrc else None
-        pa.patched_mask = _p(patched_mask)
-        pa.ident, pa.mask_sum = self.ident.data_ptr(), self.mask_sum.data_ptr()
-        pa.geo = self.geo.data_ptr()
-        pa.B, pa.H, pa.W, pa.S, pa.nsrc = self.B, self.H, self.W, self.S, self.nsrc
-
-    def prefetch(self, img0, srcs, patched_mask):
-        self._set_inputs(img0, srcs, patched_mask)
-        self._input_only(img0, C.byref(self._pa), stream_ptr())
-        self._prefetched = self._key(img0, srcs, patched_mask)
-
-    def _input_only(self, img0, pa, st):
-        if getattr(self, "_clean_acc", False):
-            _join_pack(img0.device)
-        else:
-            self.acc.zero_()
-        self._clean_acc = False
-        if self._pyr_n:
-            check(lib.fs_color_pyramid_multi(img0.data_ptr(), self._pyr_outs, self._pyr_hs, self._pyr_ws, self._pyr_n,
-                                             self.B, self.H, self.W, st), "color_pyramid_multi")
-        check(lib.fs_photo_multi_identity(pa, st), "photo_multi_identity")
-
-    def _fill(self, img0, srcs, patched_mask, depths, disps, noise_seed, gout):
-        pa, sa = self._pa, self._sa
-        self._set_inputs(img0, srcs, patched_mask)
-        pa.no_overlap_mask = 0 if self.overlapped_mask else 1
-        pa.pred, pa.ov, pa.sel = _p(self.pred), _p(self.ov), self.sel.data_ptr()
-        pa.loss_sums = self.loss_sums.data_ptr()
-        pa.dP = self.dP.data_ptr()
-        pa.gout = _p(gout)
-        pa.noise_seed = -1 if noise_seed is None else int(noise_seed)
-        pa.noise_seed_ptr = self.seed_buf.data_ptr() if noise_seed is None else None
-        pa.motion_mask = _p(self.motion_mask)
-        sa.disp_sum, sa.sm_sums, sa.dot = self.disp_sum.data_ptr(), self.sm_sums.data_ptr(), self.dot.data_ptr()
-        sa.gout = _p(gout)
-        sa.B, sa.S = self.B, self.S
-        for i, (h, w) in enumerate(self.hw):
-            pa.depth[i] = depths[i].data_ptr()
-            pa.dh[i], pa.dw[i] = h, w
-            pa.d_depth[i] = self.d_depth[i].data_ptr()
-            sa.disp[i] = disps[i].data_ptr()
-            sa.color[i] = (img0 if self.scales[i] == 0 else self.pyr[i]).data_ptr()
-            sa.d_disp[i] = self.d_disp[i].data_ptr()
-            sa.h[i], sa.w[i], sa.scale_id[i] = h, w, self.scales[i]
-
-    def forward(self, img0, srcs, P2, Ts, patched_mask, depths, disps, noise_seed=-1, motion_mask=None):
-        """img0, srcs[nsrc]: NCHW fp32; P2 [B,3,4] fp32; Ts[nsrc]: [B,4,4] fp32; the rest as PhotometricLoss.forward"""
-        st = stream_ptr()
-        N = self.nsrc
-        assert len(srcs) == N and len(Ts) == N
-        if motion_mask is not None:
-            assert motion_mask.dtype == torch.float32 and motion_mask.is_contiguous() and motion_mask.shape == (self.B, self.H, self.W)
-        self.motion_mask = motion_mask
-        assert img0.is_contiguous() and all(s.is_contiguous() for s in srcs) and all(T.is_contiguous() for T in Ts)
-        if patched_mask is not None:
-            assert patched_mask.dtype == torch.float64 and patched_mask.is_contiguous()
-        self._keep = (img0, srcs, patched_mask, depths, disps, noise_seed)
-        self._fill(img0, srcs, patched_mask, depths, disps, noise_seed, None)
-        pre, self._prefetched = self._prefetched, None
-        have_inputs = pre == self._key(img0, srcs, patched_mask)
-        pa, sa = C.byref(self._pa), C.byref(self._sa)
-        for f in range(4):
-            self._Tp[f] = Ts[f].data_ptr() if f < N else None
-        check(lib.fs_photo_multi_setup(P2.data_ptr(), self._Tp, N, self.geo.data_ptr(), self.B,
-                                       self.seed_buf.data_ptr() if noise_seed is None else None, st), "photo_multi_setup")
-        if not have_inputs:
-            self._input_only(img0, pa, st)
-        fork = self._fork(img0.device)
-        if fork is not None:          # the smoothness term beside the photometric kernels (PhotometricLoss.forward)
-            fork[1].wait_stream(fork[0])
-            with torch.cuda.stream(fork[1]):
-                st2 = stream_ptr()
-                check(lib.fs_smooth_mean(sa, st2), "smooth_mean")
-                check(lib.fs_smooth_fwd(sa, st2), "smooth_fwd")
-        else:
-            check(lib.fs_smooth_mean(sa, st), "smooth_mean")
-            check(lib.fs_smooth_fwd(sa, st), "smooth_fwd")
-        N_px = float(self.B * self.H * self.W)
-        # algorithmic bytes: per scale, target 12 Npx + nsrc sources 12 nsrc Npx + depth 4 Npx / 4^s + result 4 Npx
-        fwd_bytes = sum(12.0 * (N + 1) * N_px + 4.0 * N_px + 4.0 * N_px / (4 ** s) for s in self.scales)
-        _timed("photo_multi_fwd", fwd_bytes, lambda: check(lib.fs_photo_multi_fwd(pa, st), "photo_multi_fwd"))
-        if fork is not None:
-            fork[0].wait_stream(fork[1])
-        self.out = torch.empty(2 * self.S + 1, dtype=torch.float64, device=img0.device)
-        self.total = torch.empty((), dtype=torch.float64, device=img0.device)
-        check(lib.fs_loss_finalize(self.loss_sums.data_ptr(), self.mask_sum.data_ptr(), self.sm_sums.data_ptr(), sa,
-                                   self.out.data_ptr(), self.total.data_ptr(), st), "loss_finalize")
-        return self.out
-
-    def backward(self, gout=None):
-        st = stream_ptr()
-        img0, srcs, patched_mask, depths, disps, noise_seed = self._keep
-        self._fill(img0, srcs, patched_mask, depths, disps, noise_seed, gout)
-        pa, sa = C.byref(self._pa), C.byref(self._sa)
-        if getattr(self, "_clean_dd", False):
-            _join_pack(img0.device)
-        else:
-            self._dd_flat.zero_()
-        self._clean_dd = False
-        fork = self._fork(img0.device)
-        if fork is not None:
-            fork[1].wait_stream(fork[0])
-            with torch.cuda.stream(fork[1]):
-                check(lib.fs_smooth_bwd(sa, stream_ptr()), "smooth_bwd")
-        N_px = float(self.B * self.H * self.W)
-        bwd_bytes = sum(12.0 * (self.nsrc + 1) * N_px + 4.0 * N_px + 8.0 * N_px / (4 ** s) for s in self.scales)
-        _timed("photo_multi_bwd", bwd_bytes, lambda: check(lib.fs_photo_multi_bwd(pa, st), "photo_multi_bwd"))
-        check(lib.fs_photo_multi_pose_grad(self.geo.data_ptr(), self.dP.data_ptr(), self._dT.data_ptr(), self.nsrc,
-                                           self.B, self.S, self.bwd_tiles, st), "photo_multi_pose_grad")
-        if fork is not None:
-            fork[0].wait_stream(fork[1])
-        else:
-            check(lib.fs_smooth_bwd(sa, st), "smooth_bwd")
-        return self.d_depth, self.d_disp, self.dT
+        super().__init__(B, H, W, scales, device, min_depth, max_depth, want_pred=want_pred,
+                         overlapped_mask=overlapped_mask, nsrc=nsrc, force_multi=True)
 
 
 def sumsq(g, out, step_counter=None):

@@ -14,37 +14,8 @@ _UNSUPPORTED_FLAGS = ("is_residual_flow", "is_light_compensate", "learnable_phot
 
 
 class _PhotoLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pl, S, img0, src_a, src_b, P2, patched_mask, motion_mask, T_a, T_b, *dd):
-        ctx.set_materialize_grads(False)
-        depths = [d.contiguous().float() for d in dd[:S]]
-        disps = [d.contiguous().float() for d in dd[S:]]
-        seed = None if RT.tie_noise else -1     # None: device-resident seed, bumped in-stream every step
-        RT.mark("photo.fwd.start")
-        out = pl.forward(img0.contiguous().float(), [src_a.contiguous().float(), src_b.contiguous().float()],
-                         P2.contiguous().float(), [T_a.contiguous().float(), T_b.contiguous().float()], patched_mask,
-                         depths, disps, noise_seed=seed,
-                         motion_mask=None if motion_mask is None else motion_mask.contiguous().float())
-        ctx.pl, ctx.S = pl, S
-        vec = out                       # fresh tensors of this call (ops.PhotometricLoss.forward): no copies
-        ctx.mark_non_differentiable(vec)
-        return pl.total, vec
-
-    @staticmethod
-    def backward(ctx, g_total, _g_vec):
-        pl, S = ctx.pl, ctx.S
-        gout = None
-        if g_total is not None:
-            gout = g_total.detach().double().contiguous()
-        RT.mark("photo.bwd.start")
-        d_depth, d_disp, dT = pl.backward(gout)
-        RT.mark("photo.bwd.end")
-        return (None, None, None, None, None, None, None, None, dT[0], dT[1]) + tuple(d_depth) + tuple(d_disp)
-
-
-class _PhotoLossMultiFn(torch.autograd.Function):
-    """_PhotoLossFn over a list of source frames: (pl, S, N, img0, P2, patched_mask, motion_mask, src_1..N, T_1..N,
-    depths, disps); the gradient of the transforms comes back per frame"""
+    """(pl, S, N, img0, P2, patched_mask, motion_mask, src_1..N, T_1..N, depths, disps); the gradient of the transforms
+    comes back per frame"""
 
     @staticmethod
     def forward(ctx, pl, S, N, img0, P2, patched_mask, motion_mask, *rest):
@@ -54,12 +25,12 @@ class _PhotoLossMultiFn(torch.autograd.Function):
         dd = rest[2 * N:]
         depths = [d.contiguous().float() for d in dd[:S]]
         disps = [d.contiguous().float() for d in dd[S:]]
-        seed = None if RT.tie_noise else -1
+        seed = None if RT.tie_noise else -1     # None: device-resident seed, bumped in-stream every step
         RT.mark("photo.fwd.start")
         out = pl.forward(img0.contiguous().float(), srcs, P2.contiguous().float(), Ts, patched_mask, depths, disps,
                          noise_seed=seed, motion_mask=None if motion_mask is None else motion_mask.contiguous().float())
         ctx.pl, ctx.S, ctx.N = pl, S, N
-        ctx.mark_non_differentiable(out)
+        ctx.mark_non_differentiable(out)    # fresh tensors of this call (ops.PhotometricLoss.forward): no copies
         return pl.total, out
 
     @staticmethod
@@ -155,11 +126,6 @@ class MonoDepth2Decoder(nn.Module):
             raise NotImplementedError("frame_ids %r: the HIP loss chain takes at most %d source frames, got %d"
                                       % (ids, self.MAX_SOURCES, len(ids) - 1))
 
-    @property
-    def _two_sources(self):
-        """frame_ids = [0, a, b]: the two-source kernels (photo_fused.hip); every other count runs photo_multi.hip"""
-        return len(self.frame_ids) == 3
-
     def _loss_engine(self, img0):
         B, _, H, W = img0.shape
         return self._loss_engine_for(B, H, W, img0.device)
@@ -170,11 +136,9 @@ class MonoDepth2Decoder(nn.Module):
             # the warped images only reach HBM when somebody looks at them (logging; output_dict entries below)
             kw = dict(want_pred=bool(getattr(self, "is_log_image", True) or getattr(self, "keep_warped_images", False)),
                       overlapped_mask=bool(getattr(self, "overlapped_mask", False)))
-            if self._two_sources:
-                self._pl = ops.PhotometricLoss(B, H, W, self.scales, device, self.min_depth, self.max_depth, **kw)
-            else:
-                self._pl = ops.PhotometricLossMulti(B, H, W, self.scales, device, self.min_depth, self.max_depth,
-                                                    len(self.frame_ids) - 1, **kw)
+            # (frame_ids = [0, a, b] runs the two-source kernels, every other count the N-frame ones)
+            self._pl = ops.PhotometricLoss(B, H, W, self.scales, device, self.min_depth, self.max_depth,
+                                           nsrc=len(self.frame_ids) - 1, **kw)
             self._pl_key = key
         return self._pl
 
@@ -231,16 +195,8 @@ class MonoDepth2Decoder(nn.Module):
         Ts = [output_dict[("cam_T_cam", f)] for f in sources]
         # (what the loss differentiates: the training hook's per-chain capture cuts the backward here)
         self._loss_inputs = (Ts, depths + disps)
-        if self._two_sources:
-            fa, fb = sources
-            total, vec = _PhotoLossFn.apply(self._pl, S, img0, input_dict[("original_image", fa)],
-                                            input_dict[("original_image", fb)], input_dict["P2"], pm,
-                                            input_dict.get("motion_mask", None), Ts[0], Ts[1], *depths, *disps)
-        else:
-            total, vec = _PhotoLossMultiFn.apply(self._pl, S, N, img0, input_dict["P2"], pm,
-                                                 input_dict.get("motion_mask", None),
-                                                 *[input_dict[("original_image", f)] for f in sources], *Ts,
-                                                 *depths, *disps)
+        total, vec = _PhotoLossFn.apply(self._pl, S, N, img0, input_dict["P2"], pm, input_dict.get("motion_mask", None),
+                                        *[input_dict[("original_image", f)] for f in sources], *Ts, *depths, *disps)
         losses = {}
         for k, s in enumerate(self.scales):
             losses["loss/%d" % s] = vec[k]

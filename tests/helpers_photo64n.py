@@ -345,7 +345,7 @@ def shapes_b(st):
     return tuple(out + [b for b in both if b not in out])
 
 
-SHAPES_A = ((24, 64, 2), (40, 72, 2))                    # all four scales through ops.PhotometricLossMulti, N = 1, 3, 4
+SHAPES_A = ((24, 64, 2), (40, 72, 2))                    # all four scales through ops.PhotometricLoss, N = 1, 3, 4
 CASES_C = {4: (33, 61, ((33, 61), (16, 30), (9, 17), (4, 7))), 3: (20, 70, ((1, 1), (1, 9), (7, 1)))}
 SHAPE_D = (40, 72, 2)                                    # the option runs, N = 3
 N1_SWEEP = 4                                             # N = 1 runs four shapes of the sweep: the first, middle and last multi-strip one and the last single-strip one

@@ -230,19 +230,25 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
 
 def test_photo_multi_kernels_do_not_spill(tmp_path):
     """photo_multi.hip compiled to assembly with the library's flags, as tests/test_no_spills_cpu.py compiles its kernels:
-    the two resource-summary numbers of every kernel"""
+    the two resource-summary numbers of every kernel.  Setup, identity planes and pose gradient of the N-frame entry points
+    are kernels of photometric.hip: the same two numbers over that file."""
     from fsnet_amd.csrc import build as Bd
-    src = os.path.join(Bd.HERE, "photo_multi.hip")
-    out = str(tmp_path / "photo_multi.s")
-    cmd = [Bd.HIPCC] + Bd.FLAGS + Bd.extra_flags(src) + ["--cuda-device-only", "-S", src, "-o", out]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    asm = open(out).read()
-    spills = [int(v) for v in re.findall(r"\.vgpr_spill_count:\s+(\d+)", asm)]
-    scratch = [int(v) for v in re.findall(r"; ScratchSize: (\d+)", asm)]
-    assert len(spills) == 6 and len(scratch) == 6, (spills, scratch)      # setup, identity, pose-grad, backward, 2 x forward
-    assert all(v == 0 for v in spills), spills
-    assert all(v <= 128 for v in scratch), scratch
+    # photo_multi.hip: backward, 2 x forward; photometric.hip: setup, tile identity, pose-grad, identity rows x 2 policies
+    for name, count in (("photo_multi", 3), ("photometric", 5)):
+        src = os.path.join(Bd.HERE, name + ".hip")
+        out = str(tmp_path / (name + ".s"))
+        cmd = [Bd.HIPCC] + Bd.FLAGS + Bd.extra_flags(src) + ["--cuda-device-only", "-S", src, "-o", out]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        asm = open(out).read()
+        spills = [int(v) for v in re.findall(r"\.vgpr_spill_count:\s+(\d+)", asm)]
+        scratch = [int(v) for v in re.findall(r"; ScratchSize: (\d+)", asm)]
+        assert len(spills) == count and len(scratch) == count, (name, spills, scratch)
+        assert all(v == 0 for v in spills), (name, spills)
+        assert all(v <= 128 for v in scratch), (name, scratch)
+        for k in (("photo_multi_bwd_kernel", "photo_multi_fwd_kernel") if name == "photo_multi" else
+                  ("photo_setup_kernel", "photo_pose_grad_kernel", "photo_ident_rows_kernelINS_7NFrames")):
+            assert k in asm, (name, k)
 
 
 # --------------------------------------------------------------------------------------------- the decoder's options

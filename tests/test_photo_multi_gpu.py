@@ -31,14 +31,15 @@ def _on_dev(case, opts, dev):
 
 
 def run_ops(dev, case, opts, want_pred=True, noise_seed=-1):
-    """forward + backward through ops.PhotometricLossMulti (maps = (H >> s, W >> s)); pred / ov / sel pre-filled with
-    NaN / 255 / 255 so that an unwritten cell shows"""
+    """forward + backward through ops.PhotometricLoss on the N-frame kernels, N = 2 included (maps = (H >> s, W >> s));
+    pred / ov / sel pre-filled with NaN / 255 / 255 so that an unwritten cell shows"""
     from fsnet_amd.hip import ops
     B, H, W, S, N = case["B"], case["H"], case["W"], len(case["maps"]), len(case["src"])
     assert list(case["maps"]) == [(H >> s, W >> s) for s in range(S)]
     d = _on_dev(case, opts, dev)
-    pl = ops.PhotometricLossMulti(B, H, W, list(range(S)), dev, 0.5, 100.0, N, want_pred=want_pred,
-                                  overlapped_mask=opts.get("overlapped_mask", True))
+    pl = ops.PhotometricLoss(B, H, W, list(range(S)), dev, 0.5, 100.0, nsrc=N, force_multi=True, want_pred=want_pred,
+                             overlapped_mask=opts.get("overlapped_mask", True))
+    assert pl.multi
     if want_pred:
         pl.pred.fill_(float("nan"))
         pl.ov.fill_(255)

@@ -60,7 +60,7 @@ def main():
                            ("multi-4", 4, True)):
         inp = make_inputs(B, H, W, N, dev)
         if multi:
-            pl = ops.PhotometricLossMulti(B, H, W, [0, 1, 2, 3], dev, 0.5, 100.0, N, want_pred=False)
+            pl = ops.PhotometricLoss(B, H, W, [0, 1, 2, 3], dev, 0.5, 100.0, nsrc=N, force_multi=True, want_pred=False)
         else:
             pl = ops.PhotometricLoss(B, H, W, [0, 1, 2, 3], dev, 0.5, 100.0, want_pred=False)
         variants[name] = (pl, inp, N)
@@ -78,7 +78,7 @@ def main():
         pl, _, N = variants[name]
         chain(name)                           # fills the argument struct
         pa, st = C.byref(pl._pa), stream_ptr()
-        multi = isinstance(pl, ops.PhotometricLossMulti)
+        multi = pl.multi
         calls = {
             "identity": (lambda: lib.fs_photo_multi_identity(pa, st)) if multi else (lambda: lib.fs_photo_identity_rows(pa, st)),
             "forward": (lambda: lib.fs_photo_multi_fwd(pa, st)) if multi else (lambda: lib.fs_photo_fused_fwd(pa, st)),
