@@ -54,7 +54,7 @@ class DataParallelContext:
         #   companion  on the chains' companion streams as in the single-GPU step — a bucket's all-reduce then waits for the
         #              chain and for every companion holding work;
         #   tail       inline, except the depth decoder's, which run at the tail of the pose chain's stream when the backward
-        #              has been issued (the depth chain — decoder, then encoder — is the longer one: nets.flush_tail).
+        #              has been issued (the depth chain — decoder, then encoder — is the longer one: HO.flush_tail).
         # FSNET_AMD_DP_WGRAD names one; "auto" (default) lets the training hook's autotune time them on the ranks present.
         self.wgrad_env = os.environ.get("FSNET_AMD_DP_WGRAD", "auto").lower()
         assert self.wgrad_env in ("auto", "inline", "companion", "tail"), self.wgrad_env
@@ -124,8 +124,8 @@ class DataParallelContext:
         self._expected = {}
         self.n_small = self.n_bucket = 0
         # bias sums a backward that raised left behind would be flushed into this step's freshly zeroed gradients
-        from .nets import drop_inline_bias
-        drop_inline_bias()
+        from .handover import HO
+        HO.drop_inline_bias()
 
     def note_forward(self, module):
         """a network ran a training forward: its gradients must be reduced before finish()"""
@@ -139,9 +139,9 @@ class DataParallelContext:
         return ent[1]
 
     def _reduce_range(self, arena, lo, hi):
+        from .handover import HO
         if arena.grad.is_cuda:
-            from .nets import flush_inline_bias
-            flush_inline_bias(torch.cuda.current_stream(arena.grad.device))   # bias sums collected along this chain
+            HO.flush_inline_bias(torch.cuda.current_stream(arena.grad.device))   # bias sums collected along this chain
         if hi <= lo:
             return
         self.n_bucket += 1
@@ -149,7 +149,6 @@ class DataParallelContext:
         if self._direct is not None:
             # the bucket's weight gradients were issued on the current (chain) stream: the communication stream
             # picks up from there, the chain goes on with the rest of the backward
-            from .nets import flush_deferred, late_call, pending_companions
             cur = torch.cuda.current_stream(g.device)
             comm, companions = self._comm_stream, self.wgrad_companions
 
@@ -159,23 +158,22 @@ class DataParallelContext:
                 else:
                     comm.wait_event(ev)
                 if companions:
-                    for ws in pending_companions():
+                    for ws in HO.pending_companions():
                         comm.wait_stream(ws)
                 with torch.cuda.stream(comm):
                     self._direct.all_reduce_sum(g)
             if companions:
-                flush_deferred(cur)                  # what the chain still holds goes to its companion (inside a capture:
-            #                                          at the end of the pass, the bucket behind it — nets.flush_deferred)
-            if not late_call(cur, reduce_bucket):
+                HO.flush_deferred(cur)               # what the chain still holds goes to its companion (inside a capture:
+            #                                          at the end of the pass, the bucket behind it — HO.flush_deferred)
+            if not HO.late_call(cur, reduce_bucket):
                 if companions:
-                    flush_deferred(cur, now=True)
+                    HO.flush_deferred(cur, now=True)
                 reduce_bucket()
             return
-        from .nets import flush_deferred, join_companions
         if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("torch.distributed gradient buckets cannot be captured into a hipGraph")
-        flush_deferred(now=True)  # weight-gradient kernels handed to companion streams must have landed in the
-        join_companions()         # arena slice before it is reduced
+        HO.flush_deferred(now=True)  # weight-gradient kernels handed to companion streams must have landed in the
+        HO.join_companions()         # arena slice before it is reduced
         self.handles.append(dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
 
     def partial_ready(self, module, sub_modules):

@@ -16,6 +16,7 @@ import torch
 from ..hip import ops
 from ..hip.binding import raw_stream
 from ..hip.conv import ConvOp, run_specs
+from .handover import HO
 from .runtime import RT, grad_of
 
 STAT_SLOTS = ops.STAT_SLOTS
@@ -86,395 +87,6 @@ class StatsPool:
         return v
 
 
-_PENDING_JOIN = set()   # (chain stream, companion stream) pairs with weight-gradient work in flight
-_PENDING_KEEP = []      # tensors the companion kernels still read: kept alive until the join (no record_stream
-                        # bookkeeping in the allocator, and safe inside a hipGraph capture's private pool)
-_DEFERRED = {}          # chain stream id -> (chain stream, [weight-gradient work items not yet handed over])
-_CALLBACK_QUEUED = [None]     # id of the backward pass whose end-of-backward callback is queued
-_ACTIVE_CHAINS = set()  # chain stream ids that deferred work during the running backward pass
-
-
-_STREAM_OBJS = {}
-
-
-def _current_stream(device=None):
-    """torch's current Stream object, cached by raw handle (building one costs ~6 us; 60+ lookups per step)"""
-    from ..hip.binding import raw_stream
-    idx = torch.cuda.current_device() if device is None or device.index is None else device.index
-    key = (idx, raw_stream(idx))
-    s = _STREAM_OBJS.get(key)
-    if s is None:
-        s = _STREAM_OBJS[key] = torch.cuda.current_stream(idx)
-    return s
-
-
-def _run_param_grads(*item, bias_later=None):
-    """one layer's weight (+ bias) gradient — item = (op, dc, x, gw, gb, nb, pro) — or the same layer of two networks in
-    one launch — item = ("lanes", [those tuples]) (fs_conv_wgrad2: one round of blocks, one slab arena, two dW)"""
-    lanes = item[1] if item[0] == "lanes" else [item]
-    run_specs([op.wgrad_spec(dc, x, gw, pro=pro) for (op, dc, x, gw, gb, nb, pro) in lanes])
-    for (op, dc, x, gw, gb, nb, pro) in lanes:
-        if gb is not None:
-            if bias_later is not None:
-                bias_later.append((dc, gb, nb))     # (the caller sums the batch's biases in one launch)
-            else:
-                ops.channel_sum(dc, gb, nb)
-
-
-_INLINE_BIAS = {}       # chain stream id -> (chain stream, [(dc, gb, nb)]): bias sums of inline weight gradients not yet issued
-
-
-def _inline_bias_list(dev):
-    """data parallel: the weight gradients run inline on their chain — their bias sums are still collected and issued as
-    one launch per gradient bucket (flush_inline_bias from DataParallelContext._reduce_range) instead of one per layer
-    (18 launches of ~10 us on the decoders' chains: tools/probes/dp_world1.py)"""
-    if not (RT.dp is not None and dev.type == "cuda"):
-        return None
-    cur = _current_stream(dev)
-    return _INLINE_BIAS.setdefault(cur.cuda_stream, (cur, []))[1]
-
-
-def drop_inline_bias():
-    """a new step begins (DataParallelContext.begin_step): whatever a backward that raised left uncollected is not this
-    step's gradient"""
-    for ent in _INLINE_BIAS.values():
-        ent[1].clear()
-
-
-def flush_inline_bias(cur=None):
-    """issue the collected bias sums of chain stream `cur` (default: every chain) on their chain"""
-    for key in ([cur.cuda_stream] if cur is not None else list(_INLINE_BIAS.keys())):
-        ent = _INLINE_BIAS.get(key)
-        if ent is None or not ent[1]:
-            continue
-        chain, items = ent
-        with torch.cuda.stream(chain):
-            ops.channel_sum_multi(items)
-        items.clear()
-
-
-def accumulate_param_grads_multi(cls, ops_, dcs, xs, pros):
-    """ConvLayer.accumulate_param_grads for the same layer of the lanes of an EncoderPass: the lanes whose weights are
-    trained share one weight-gradient launch (deferred to the companion stream like a single layer's)"""
-    lanes = []
-    for cl, op, dc, x, pro in zip(cls, ops_, dcs, xs, pros):
-        gw = grad_of(cl.m.weight)
-        gb = grad_of(cl.m.bias) if cl.m.bias is not None else None
-        if gw is None:                       # frozen layer: nothing to accumulate (a lone trainable bias: its sum)
-            if gb is not None:
-                ops.channel_sum(dc, gb, cl.m.bias.numel())
-            continue
-        lanes.append((op, dc, x, gw, gb, cl.m.bias.numel() if gb is not None else 0, pro))
-    if not lanes:
-        return
-    item = lanes[0] if len(lanes) == 1 else ("lanes", lanes)
-    dc0 = lanes[0][1]
-    mode = RT.wgrad_streams if (dc0.is_cuda and RT.overlap and (RT.dp is None or RT.dp.wgrad_companions)) else 0
-    if mode:
-        _defer_param_grads(_current_stream(dc0.device), item)
-        return
-    _run_param_grads(*item, bias_later=_inline_bias_list(dc0.device))
-
-
-def _drop_stale():
-    """leftovers of a backward pass that raised (its end-of-backward callback never ran): not this pass's gradients"""
-    if _CALLBACK_QUEUED[0] is not None and _CALLBACK_QUEUED[0] != torch._C._current_graph_task_id():
-        for stale in _DEFERRED.values():
-            stale[1].clear()
-        _ACTIVE_CHAINS.clear()
-        _LATE.clear()
-        _AT_END.clear()
-
-
-def _defer_param_grads(cur, item):
-    _drop_stale()
-    ent = _DEFERRED.get(cur.cuda_stream)
-    if ent is None:
-        ent = _DEFERRED[cur.cuda_stream] = (cur, [])
-    ent[1].append(item)
-    _ACTIVE_CHAINS.add(cur.cuda_stream)
-    # runs once, when the autograd engine has executed every node of this backward pass and before it synchronises the
-    # streams it used with the caller's stream.  (Keyed by the pass: a backward that died in an exception never ran its
-    # callback, and must not keep the next one from queueing its own.)
-    _queue_end_of_backward()
-    if len(ent[1]) >= (RT.wgrad_flush_even if RT.even_chains else RT.wgrad_flush):
-        flush_deferred(cur)
-
-
-_BATCH_NO = [0]         # (numbering of the FSNET_AMD_MARKS=1 marks around each batch)
-HANDOVERS = {"late": 0, "shared": 0}    # batches issued late / shared with the other chain's streams (tests read it)
-_ENCODER_END = [False]  # the last two stages and the stem of an encoder's backward are being issued (EncoderPass.backward)
-_AT_END = []            # [(event, chain, [(stream, items)])]: parts of a batch issued once every node of the pass has been
-_LATE = []              # inside a hipGraph capture, put off: [(event on the chain, chain, companion, items, position)] batches,
-                        # [(event, chain, None, fn, position)] calls (late_call)
-_CHAINS_BEGUN = [None, []]    # backward pass (graph task id), chain streams whose backward has begun in it
-
-
-def _issue_batch(chain, ws, mine, ev=None):
-    """weight-gradient items of `chain` on stream `ws`, behind the chain (ev: behind an event recorded on it earlier)"""
-    if ev is None:
-        ws.wait_stream(chain)                   # one cross-stream edge per batch
-    else:
-        ws.wait_event(ev)
-    with torch.cuda.stream(ws):
-        if RT._marks is not None:
-            _BATCH_NO[0] += 1
-            tag = "wg.%s.%d" % ("pose" if RT.is_side(chain) else "depth", _BATCH_NO[0])
-            RT.mark(tag + ".start")
-        sums = []
-        for it in mine:
-            _run_param_grads(*it, bias_later=sums)
-        if sums:
-            ops.channel_sum_multi(sums)         # the batch's bias gradients in one launch
-        if RT._marks is not None:
-            RT.mark(tag + ".end(%d)" % len(mine))
-    _PENDING_JOIN.add((chain, ws))
-
-
-def _position(chain):
-    """token of `chain`'s position in the running capture (fs_capture_position: changes whenever the stream captures a node)"""
-    import ctypes as C
-    from ..hip.binding import check, lib
-    tok = C.c_ulonglong(0)
-    check(lib.fs_capture_position(C.c_void_p(chain.cuda_stream), C.byref(tok)), "fs_capture_position")
-    return tok.value
-
-
-def issue_late(chain=None, advanced=False):
-    """issue what was put off on `chain` (default: every chain) inside a capture, in the order it was put off: weight-
-    gradient batches (flush_deferred) and gradient-bucket reductions (late_call, from DataParallelContext._reduce_range).
-    advanced: only what was put off at an EARLIER position of the chain than its current one — the chain has captured its
-    next kernel since, which is all the putting-off is for (flush_deferred); what was put off where the chain still stands
-    stays."""
-    if not _LATE:
-        return
-    mine = [e for e in _LATE if chain is None or e[1].cuda_stream == chain.cuda_stream]
-    if advanced and mine:
-        here = _position(chain)
-        mine = [e for e in mine if e[4] != here]
-    if not mine:
-        return
-    ids = {id(e) for e in mine}
-    _LATE[:] = [e for e in _LATE if id(e) not in ids]
-    for ent in mine:
-        if ent[2] is None:
-            ent[3](ent[0])                      # fn(event recorded on the chain where the call was put off)
-        else:
-            _issue_batch(ent[1], ent[2], ent[3], ev=ent[0])
-
-
-def issue_advanced(device):
-    """a cheap place to let go of what the current chain put off (block and level boundaries of the backward passes): under
-    data parallelism a bucket's all-reduce takes its place in the communicator's launch order when it is ISSUED, and one
-    issued at the end of the pass would run after every SyncBN exchange of the backward instead of beside it"""
-    if _LATE:
-        _drop_stale()
-        issue_late(_current_stream(device), advanced=True)
-
-
-def late_call(chain, fn):
-    """inside a capture: call fn(event) when every node of the backward pass has been issued (see flush_deferred) —
-    `event` is recorded on `chain` now, and what fn issues on another stream behind it becomes a LATER successor of the
-    chain's last node than the chain's next kernel.  Returns False, and does nothing, outside a capture or an autograd
-    pass."""
-    if not (RT.wgrad_late and torch.cuda.is_current_stream_capturing() and torch._C._current_graph_task_id() >= 0):
-        return False
-    _drop_stale()
-    issue_late(chain, advanced=True)
-    ev = torch.cuda.Event()
-    ev.record(chain)
-    _LATE.append((ev, chain, None, fn, _position(chain)))
-    _queue_end_of_backward()
-    return True
-
-
-def flush_deferred(cur=None, now=False):
-    """hand the collected weight-gradient work of chain stream `cur` (default: all chains) to its companion.
-
-    Inside a hipGraph capture the batch's kernels are ISSUED later (`now`: at once) — at the chain's next hand-over or block
-    boundary that finds it further on (issue_late(advanced=True)), at the latest when the whole backward pass has been
-    issued — behind the event recorded here.  Dependencies are the same; what changes is the ORDER of the edges that leave
-    the chain's last node: the chain's next kernel becomes its first successor, the batch its second.  The HIP graph executor
-    (ROCm 7.2) hands out its 4 streams by a depth-first walk in which a node's first successor stays on the node's stream and
-    the k-th further one goes k streams on (mod 4); each stream runs its nodes in the order they were captured.  With the
-    batch first, the weight gradients inherited the chain's stream and the chain hopped to one where it queued behind
-    whatever the other chain had there (docs/LAB_r06.md, "the executor's stream assignment": DEBUG_HIP_GRAPH_DOT_PRINT
-    dumps read with tools/probes/graph_streams.py)."""
-    late = (RT.wgrad_late and not now and torch.cuda.is_current_stream_capturing()
-            and torch._C._current_graph_task_id() >= 0)
-    for key in ([cur.cuda_stream] if cur is not None else list(_DEFERRED.keys())):
-        ent = _DEFERRED.get(key)
-        if ent is None or not ent[1]:
-            continue
-        chain, items = ent
-        issue_late(chain, advanced=late)        # (what was put off goes first: the companion runs batches in this order)
-        ws = RT.companion_stream(chain.device, chain)[1]
-        ev = None
-        capturing = late or torch.cuda.is_current_stream_capturing()
-        if capturing:
-            ev = torch.cuda.Event()
-            ev.record(chain)
-        mine = list(items)
-        if (RT.wgrad_balance and RT.even_chains and capturing and _ENCODER_END[0] and RT.dp is None and not RT.is_side(chain)
-                and len(items) >= 2 and torch._C._current_graph_task_id() >= 0):
-            # the end of the main chain's encoder: the chain's companion still has the depth decoder's weight gradients to
-            # run when the encoder's arrive, and ends the step with them after the pose chain and its companion have
-            # finished.  Half of each batch from layer2 on goes to the pose chain's stream, issued at the end of the pass
-            # like everything else — behind the pose chain's own work; as the third successor of the hand-over point the
-            # share lands on the executor's stream of the pose chain.  (Shares of the encoder's earlier batches run
-            # beside the depth chain rather than after it: measured, they slow it more than they relieve the companion.)
-            side = RT.side_stream(chain.device)
-            others = [side, RT.companion_stream(chain.device, side)[1]][:RT.wgrad_balance]
-            n = 1 + len(others)
-            _AT_END.append((ev, chain, [(o, items[1 + k::n]) for k, o in enumerate(others)]))
-            HANDOVERS["shared"] += 1
-            mine = items[0::n]
-        if late:
-            _LATE.append((ev, chain, ws, mine, _position(chain)))
-            HANDOVERS["late"] += 1
-        else:
-            _issue_batch(chain, ws, mine, ev=ev)
-        _PENDING_KEEP.extend(items)
-        ent[1].clear()
-    if not late:
-        issue_late(cur)
-
-
-def chain_ends(device):
-    """a chain has issued its last kernel (the end of an encoder's backward).  Inside a capture, with hand-overs put off: one
-    empty launch on the chain, so that the last hand-over point has a first successor that stays on the chain's stream like
-    every other one — otherwise the last batch inherits the chain's executor stream and the share that follows it the
-    companion's, behind the companion's backlog."""
-    if (RT.wgrad_late and (_LATE or _AT_END) and device.type == "cuda" and torch.cuda.is_current_stream_capturing()
-            and torch._C._current_graph_task_id() >= 0):
-        RT.nop(device)
-        issue_late(_current_stream(device))
-
-
-def chain_begins(device):
-    """called where a network's backward begins on its chain (the decoders' autograd nodes).  Inside a hipGraph capture,
-    when the SECOND chain of the pass begins, one empty launch is put on the first chain's companion, behind the second
-    chain's pending dependencies — a third successor of the loss backward's last node, between the two chains' first
-    kernels.  By the executor's rule (flush_deferred) the first chain then keeps that node's stream s, its weight gradients
-    get s+1, the second chain s+2 and its weight gradients s+3: four streams, one each.  Without it the second chain
-    shares s+1 with the first chain's weight gradients, behind them in launch order."""
-    if not (RT.wgrad_late and device.type == "cuda" and RT.overlap and RT.wgrad_streams
-            and torch.cuda.is_current_stream_capturing()):
-        return
-    task = torch._C._current_graph_task_id()
-    if task < 0:
-        return
-    _drop_stale()
-    if _CHAINS_BEGUN[0] != task:
-        _CHAINS_BEGUN[0], _CHAINS_BEGUN[1] = task, []
-    cur = _current_stream(device)
-    begun = _CHAINS_BEGUN[1]
-    if any(c.cuda_stream == cur.cuda_stream for c in begun):
-        return
-    begun.append(cur)
-    if len(begun) == 2:
-        first = begun[0]
-        ws = RT.companion_stream(device, first)[1]
-        ws.wait_stream(cur)
-        with torch.cuda.stream(ws):
-            RT.nop(device)
-        _PENDING_JOIN.add((first, ws))
-
-
-def _end_of_backward():
-    _CALLBACK_QUEUED[0] = None
-    flush_tail()
-    flush_inline_bias()
-    flush_deferred(now=True)
-    for ev, chain, parts in _AT_END:
-        for ws, mine in parts:
-            if mine:
-                _issue_batch(chain, ws, mine, ev=ev)
-    _AT_END.clear()
-    _ENCODER_END[0] = False
-    _ACTIVE_CHAINS.clear()
-    _BATCH_NO[0] = 0
-    join_companions()
-
-
-def join_companions():
-    """every chain stream waits for its companion.  Inside a hipGraph capture the join is left to
-    join_companions_final(): joining a companion into a stream that is itself a fork of the capture stream and
-    then joining that one crashes hipStreamEndCapture on ROCm 7.2 (tools/probes/graph_fork_probe.py, variants
-    C/D), joining every companion straight into the capture stream does not (variant G)."""
-    if not _PENDING_JOIN:
-        return
-    if torch.cuda.is_current_stream_capturing():
-        return
-    for cur, ws in list(_PENDING_JOIN):
-        cur.wait_stream(ws)
-    _PENDING_JOIN.clear()
-    _PENDING_KEEP.clear()
-
-
-_TAIL_SINK = [None]     # while a network's backward collects its weight gradients for the tail: the list they go to
-_TAIL = []              # [(event on the network's chain, device, items, runner)] waiting for the end of the backward pass
-
-
-def _queue_end_of_backward():
-    task = torch._C._current_graph_task_id()
-    if _CALLBACK_QUEUED[0] != task:
-        torch.autograd.Variable._execution_engine.queue_callback(_end_of_backward)
-        _CALLBACK_QUEUED[0] = task
-
-
-def defer_to_tail(items, runner, device):
-    """data parallel, weight gradients "tail" (DataParallelContext.wgrad_mode): the depth decoder's weight gradients — its
-    chain goes on with the depth encoder's backward and ends the step, the pose chain's stream finishes earlier — are
-    issued on the pose chain's stream once every node of the backward pass has been issued (flush_tail), behind that
-    chain's own work; the decoder's gradient bucket follows them there."""
-    if _TAIL and _CALLBACK_QUEUED[0] != torch._C._current_graph_task_id():
-        _TAIL.clear()                        # leftovers of a backward pass that raised
-    chain = _current_stream(device)
-    ev = torch.cuda.Event()
-    ev.record(chain)
-    runner.tail_pending = True
-    _TAIL.append((ev, chain, items, runner))
-    _queue_end_of_backward()
-
-
-def flush_tail():
-    for ev, chain, items, runner in _TAIL:
-        side = RT.side_stream(chain.device)
-        side.wait_event(ev)
-        with torch.cuda.stream(side):
-            sums = []
-            for it in items:
-                _run_param_grads(*it, bias_later=sums)
-            if sums:
-                ops.channel_sum_multi(sums)
-            runner.tail_pending = False
-            if RT.dp is not None and runner.m._pending == 0:
-                RT.dp.grads_ready(runner.m)          # the bucket's all-reduce picks up from this stream
-        _PENDING_JOIN.add((chain, side))             # (joined, and the operands released, like a companion's batch)
-        _PENDING_KEEP.extend(items)
-    _TAIL.clear()
-
-
-def pending_companions():
-    """companion streams with weight-gradient work in flight in this step"""
-    return {ws for _, ws in _PENDING_JOIN}
-
-
-def join_companions_final():
-    """the current stream waits for every companion with work in flight (before the optimizer reads gradients)"""
-    flush_inline_bias()
-    flush_deferred(now=True)
-    issue_late()
-    if not _PENDING_JOIN:
-        return
-    cur = torch.cuda.current_stream()
-    for ws in {ws for _, ws in _PENDING_JOIN}:
-        cur.wait_stream(ws)
-    _PENDING_JOIN.clear()
-    _PENDING_KEEP.clear()
-
-
 _PACK_REGISTRY = {}     # (dtype, device) -> [weakref to ConvLayer]: a dropped model leaves no work behind
 _PACK_TABLES = {}       # (dtype, device, tuple of pointers) -> (device table, n, total_blocks)
 
@@ -502,7 +114,7 @@ def pack_everything_async(arena):
         if arena is not None:
             arena.flush_zero()            # (a gradient memset the training hook left to the scratch-zeroing launch)
         return
-    cur = _current_stream(dev)
+    cur = RT.current_stream(dev)
     ps = RT.pack_stream(dev)
     ps.wait_stream(cur)
     with torch.cuda.stream(ps):
@@ -517,7 +129,7 @@ def join_pack(device):
     ent = _PACK_PENDING.get(device.index)
     if ent is None:
         return
-    cur = _current_stream(device)
+    cur = RT.current_stream(device)
     if cur.cuda_stream in ent[1]:
         return
     cur.wait_stream(ent[0])
@@ -627,26 +239,8 @@ class ConvLayer:
         return self._bias
 
     def accumulate_param_grads(self, op, dc, x, pro=None):
-        """wgrad + bias grad into the parameters' gradient buffers.  They feed nothing downstream in the
-        backward pass, so they run on a companion stream while the chain continues with the dgrad.
-        pro: x is a raw convolution output whose BatchNorm (+ ReLU) the weight gradient applies itself."""
-        gw = grad_of(self.m.weight)
-        gb = grad_of(self.m.bias) if self.m.bias is not None else None
-        if gw is None:                       # frozen layer: nothing to accumulate (a lone trainable bias: its sum)
-            if gb is not None:
-                ops.channel_sum(dc, gb, self.m.bias.numel())
-            return
-        item = (op, dc, x, gw, gb, self.m.bias.numel() if gb is not None else 0, pro)
-        if _TAIL_SINK[0] is not None:
-            _TAIL_SINK[0].append(item)       # (data parallel, "tail": issued when the backward pass has been issued)
-            return
-        # (data parallel: inline on the chain stream, so that one event after a stage's last weight gradient covers
-        # the arena slice its gradient bucket reduces — also inside a captured step)
-        mode = RT.wgrad_streams if (dc.is_cuda and RT.overlap and (RT.dp is None or RT.dp.wgrad_companions)) else 0
-        if mode:
-            _defer_param_grads(_current_stream(dc.device), item)
-            return
-        _run_param_grads(*item, bias_later=_inline_bias_list(dc.device))
+        """wgrad + bias grad into the parameters' gradient buffers, off the chain (HO.submit)"""
+        HO.submit([(self, op, dc, x, pro)])
 
 
 def bn_tensors(bn):
@@ -1083,7 +677,7 @@ class EncoderPass:
         return [sp.out for sp in specs]
 
     def _param_grads(self, cls, ops_, dcs, xs, pros=None):
-        accumulate_param_grads_multi(cls, ops_, dcs, xs, pros if pros is not None else [None] * self.nl)
+        HO.submit(zip(cls, ops_, dcs, xs, pros if pros is not None else [None] * self.nl))
 
     def _block_bwd(self, units, ds, bctx, dout, extra, dout_sums=None, prev=None, in_mask=None):
         """dout: gradient w.r.t. the block output.  dout_sums: set when dout came out of a data-gradient epilogue
@@ -1224,7 +818,7 @@ class EncoderPass:
         dsums = None
         for si in range(nst - 1, -1, -1):
             nblk = len(R0.stages[si])
-            _ENCODER_END[0] = si <= 1           # (layer2, layer1 and the stem: what flush_deferred may share, see there)
+            HO.at_encoder_end(si <= 1)          # (layer2, layer1 and the stem: what flush_deferred may share, see there)
             for b in range(nblk - 1, -1, -1):
                 bi -= 1
                 units = [r.stages[si][b][0] for r in self.R]
@@ -1243,7 +837,7 @@ class EncoderPass:
                     # the consumer of the returned gradient is the previous block's output BatchNorm, unless a
                     # feature gradient still has to be added to it first (stage boundary without downsample)
                     prev = (pu[2], pu[1], pu[3])
-                issue_advanced(xs[0].device)
+                HO.issue_advanced(xs[0].device)
                 if entered and bi == 0:
                     dout, dsums = self._block_bwd(units, ds, ctx["blocks"][bi], dout, extra, dout_sums=dsums, prev=None,
                                                   in_mask=in_mask)
@@ -1260,16 +854,16 @@ class EncoderPass:
                         RT.dp.partial_ready(r.m, [getattr(r.m, "layer%d" % (si + 1 + R0.first_stage))])
         if entered:
             RT.mark(tag + ".bwd.end")
-            flush_deferred(_current_stream())
-            _ENCODER_END[0] = False
-            chain_ends(xs[0].device)
+            HO.flush_deferred(RT.current_stream())
+            HO.at_encoder_end(False)
+            HO.chain_ends(xs[0].device)
             return dout
         y0 = ctx["y0"]
         add0 = [gfeats[l][0] for l in range(nl)]
         if RT.stem_flush:
             # layer 1's weight gradients go to the companion now: they run beside the stem's memory-bound passes (pooling
             # backward, both BatchNorm-backward passes: the largest tensors of the network) instead of behind them
-            flush_deferred(_current_stream())
+            HO.flush_deferred(RT.current_stream())
         if ctx.get("stem_fused"):
             # no pooling-backward launch and no gradient tensor at the stem's resolution: both BatchNorm passes gather it
             # (the ReLU mask from the raw output for every lane: the sign of the forward's own expression — no read of
@@ -1282,9 +876,9 @@ class EncoderPass:
         stems = [r.stem for r in self.R]
         self._param_grads(stems, self._ready(stems, xs), dc0, xs)
         RT.mark(tag + ".bwd.end")
-        flush_deferred(_current_stream())
-        _ENCODER_END[0] = False
-        chain_ends(xs[0].device)
+        HO.flush_deferred(RT.current_stream())
+        HO.at_encoder_end(False)
+        HO.chain_ends(xs[0].device)
 
 
 # ==============================================================================================
@@ -1331,7 +925,7 @@ class DepthDecoderRunner:
         # level (issued after that level's first kernel, so that the chain keeps its executor stream: flush_deferred).
         # Same box, with / without: headline 5.167 / 5.179 ms, ResNet-50 18.24 / 18.32, fisheye 6.48 / 6.53.
         aside = bool(RT.overlap and dev.type == "cuda" and RT.wgrad_streams)
-        cur = _current_stream(dev) if aside else None
+        cur = RT.current_stream(dev) if aside else None
         ws = RT.companion_stream(dev, cur)[1] if aside else None
         put_off, used_ws = None, False
 
@@ -1418,18 +1012,10 @@ class DepthDecoderRunner:
         K = int(m.num_output_channels)
         gfeats = [None] * 5
         bwd_pool_reset(dev)
-        chain_begins(dev)
+        HO.chain_begins(dev)
         RT.mark("ddec.bwd.start")
-        tail = RT.dp is not None and RT.dp.decoder_tail and RT.overlap and dev.type == "cuda" and \
-            torch._C._current_graph_task_id() >= 0
-        if tail:
-            _TAIL_SINK[0] = []
-        try:
+        with HO.tail_of_pass(self, dev):       # (data parallel, "tail": its weight gradients go to the end of the pass)
             return self._backward(ctx, g_depth, g_disp, g_unc, gfeats, dev, dt, K)
-        finally:
-            items, _TAIL_SINK[0] = _TAIL_SINK[0], None
-            if items:
-                defer_to_tail(items, self, dev)
 
     def _backward(self, ctx, g_depth, g_disp, g_unc, gfeats, dev, dt, K):
         m = self.m
@@ -1481,7 +1067,7 @@ class DepthDecoderRunner:
 
         Gp, _ = disp_grad(0)
         for i in range(0, 5):
-            issue_advanced(dev)
+            HO.issue_advanced(dev)
             lv = ctx["lv"][i]
             h, w = lv["h"], lv["w"]
             H2, W2 = 2 * h, 2 * w
@@ -1507,7 +1093,7 @@ class DepthDecoderRunner:
             else:
                 gfeats[4] = op0.dgrad(dc0, h, w)
         RT.mark("ddec.bwd.end")
-        flush_deferred(_current_stream())
+        HO.flush_deferred(RT.current_stream())
         return gfeats
 
 
@@ -1546,7 +1132,7 @@ class PoseDecoderRunner:
     def backward(self, ctx, dT):
         acts, x3 = ctx["acts"], ctx["x3"]
         dt, dev = acts[0].dtype, acts[0].device
-        chain_begins(dev)
+        HO.chain_begins(dev)
         RT.mark("pdec.bwd.start")
         if isinstance(ctx["invert"], tuple):
             G = len(ctx["invert"])
@@ -1566,5 +1152,5 @@ class PoseDecoderRunner:
             # the four weight gradients go to the companion now — only with the two-lane pass: with two chains the pose chain
             # is the step's tail (its encoder backward ends 0.5 ms after the depth encoder's) and the companion shares a
             # hardware queue with it: the hand-over put 0.15 ms of weight gradients in front of that chain (5.59 -> 5.52 ms)
-            flush_deferred(_current_stream())
+            HO.flush_deferred(RT.current_stream())
         return d

@@ -27,7 +27,7 @@ class _Runtime:
         # the chains are then about equally long, and the main chain's companion — which has the depth decoder's weight
         # gradients on top of the encoder's — ends the backward ~0.3 ms after everything else.  Batches of 4 instead of 8,
         # and from layer2 on the main chain's encoder leaves half of each batch to the pose chain's stream
-        # (nets.flush_deferred).  Same box, replayed steps: ResNet-18 + ResNet-18 bf16 5.26 -> 5.20 ms, ResNet-50 +
+        # (HO.flush_deferred).  Same box, replayed steps: ResNet-18 + ResNet-18 bf16 5.26 -> 5.20 ms, ResNet-50 +
         # ResNet-50 unchanged (18.2); sharing the whole encoder's batches costs that configuration 2 %, sharing with one
         # chain only (fisheye) 8 %: the shares then run beside the depth chain instead of after it.
         self.even_chains = False
@@ -35,7 +35,7 @@ class _Runtime:
         self.wgrad_balance = 1
         # inside a capture: issue what is handed over only once the chain has captured its next kernel, so that this kernel
         # is its last node's FIRST successor in the graph, and separate the two chains' first kernels by an empty launch
-        # (nets.flush_deferred, nets.chain_begins: the executor's stream assignment follows the edge order)
+        # (handover.HO.flush_deferred, .chain_begins: the executor's stream assignment follows the edge order)
         self.wgrad_late = True
         self._nop = {}
         # hand over what is pending when an encoder's backward reaches its stem (see EncoderPass.backward): with the two-lane
@@ -60,7 +60,8 @@ class _Runtime:
         # the per-step weight re-pack beside the step's weight-free head (nets.pack_everything_async)
         self.pack_overlap = True
         self._side = {}
-        self._held = {}           # raw stream handle -> Stream: every stream the engine created (see new_stream)
+        self._current = {}        # (device index, raw stream handle) -> Stream (current_stream)
+        self._held = {}          # raw stream handle -> Stream: every stream the engine created (see new_stream)
         # FSNET_AMD_MARKS=1: device-clock marks along the step (mark() below), read back with marks_report()
         self._marks = {} if os.environ.get("FSNET_AMD_MARKS", "0") != "0" else None
         self._mark_buf = None
@@ -161,6 +162,16 @@ class _Runtime:
     def release_stream(self, handle):
         """give a stream from new_stream() back (its owner is gone)"""
         self._held.pop(handle, None)
+
+    def current_stream(self, device=None):
+        """torch's current Stream object, cached by raw handle (building one costs ~6 us; 60+ lookups per step)"""
+        from ..hip.binding import raw_stream
+        idx = torch.cuda.current_device() if device is None or device.index is None else device.index
+        key = (idx, raw_stream(idx))
+        s = self._current.get(key)
+        if s is None:
+            s = self._current[key] = torch.cuda.current_stream(idx)
+        return s
 
     def pack_stream(self, device):
         """stream of the per-step weight re-pack (nets.pack_everything_async)"""

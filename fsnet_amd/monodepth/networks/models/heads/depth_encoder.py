@@ -46,7 +46,7 @@ class _DepthDecoderFn(torch.autograd.Function):
         ctx.c = None
         mod._pending -= 1
         if mod._pending == 0 and RT.dp is not None and not mod._runner.tail_pending:
-            RT.dp.grads_ready(mod)      # (tail_pending: nets.flush_tail reduces the bucket behind the weight gradients)
+            RT.dp.grads_ready(mod)      # (tail_pending: HO.flush_tail reduces the bucket behind the weight gradients)
         gf = tuple(None if t is None else t.permute(0, 3, 1, 2) for t in gfeats[: ctx.nfeat])
         return (None, None, None) + gf + (None,) * ctx.nparam
 

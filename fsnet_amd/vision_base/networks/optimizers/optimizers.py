@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 import torch.optim as optim
 
-from fsnet_amd.engine.nets import join_companions_final
+from fsnet_amd.engine.handover import HO
 from fsnet_amd.engine.runtime import RT
 from fsnet_amd.hip import ops
 
@@ -140,7 +140,7 @@ class ArenaOptimizer:
             with torch.enable_grad():
                 loss = closure()
         g0 = self.param_groups[0]
-        join_companions_final()        # weight-gradient kernels still in flight on companion streams
+        HO.join_companions_final()        # weight-gradient kernels still in flight on companion streams
         flat = self._flat_state(arena)
         runs = self._run_table(arena)
         dev = arena.data.device
@@ -176,7 +176,7 @@ class ArenaOptimizer:
 
     def _torch_step(self, closure, max_norm, grad_scale):
         """the torch.optim base class's own step, after what the training hook does in front of a plain optimizer"""
-        join_companions_final()
+        HO.join_companions_final()
         params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
         if grad_scale != 1.0:
             for p in params:
@@ -242,7 +242,7 @@ class FusedAdam(ArenaOptimizer, optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        join_companions_final()
+        HO.join_companions_final()
         params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
         sq = None
         if max_norm is not None and max_norm > 0 and params:

@@ -31,8 +31,8 @@ def _step(dev, fold, H, W, B, groups_pose=True):
         m._arena.zero_grads()
         out = m(data, dict(epoch_num=0, global_step=0, is_training=True))
         out["loss"].backward()
-        from fsnet_amd.engine.nets import join_companions_final
-        join_companions_final()
+        from fsnet_amd.engine.handover import HO
+        HO.join_companions_final()
         LaunchProfile.end()
         kinds = [k for (k, _, _, _) in LaunchProfile.tagged]
         torch.cuda.synchronize()

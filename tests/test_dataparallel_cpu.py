@@ -267,10 +267,15 @@ def test_rank_agreement_through_the_store():
 
 
 def test_hand_overs_left_by_a_backward_that_raised_are_dropped_by_the_next_pass():
-    """nets._LATE / _AT_END / _DEFERRED hold work that was put off inside a backward pass (flush_deferred, late_call); their
-    end-of-backward callback empties them.  A pass that raised never ran it: the next pass must not issue that work (events of a
-    dead capture, gradients of another step) — the first entry point it reaches drops it (nets._drop_stale)."""
-    from fsnet_amd.engine import nets
+    """HO.late / at_end / deferred / tail hold work that was put off inside a backward pass (flush_deferred, late_call,
+    defer_to_tail); their end-of-backward callback empties them.  A pass that raised never ran it: the next pass must not issue
+    that work (events of a dead capture, gradients of another step) nor feed a sink nobody empties — the first entry point it
+    reaches drops all of it (HO._drop_stale -> _reset_pass)."""
+    from fsnet_amd.engine.handover import HO, Batch, Held, LateCall, TailEntry
+
+    def counts():
+        return (len(HO.late), len(HO.at_end), sum(len(h.items) for h in HO.deferred.values()), len(HO.tail),
+                HO.tail_sink, HO.encoder_end, sum(len(h.items) for h in HO.inline_bias.values()))
 
     class Probe(torch.autograd.Function):
         @staticmethod
@@ -279,26 +284,39 @@ def test_hand_overs_left_by_a_backward_that_raised_are_dropped_by_the_next_pass(
 
         @staticmethod
         def backward(ctx, g):
-            nets._drop_stale()
-            Probe.seen = (len(nets._LATE), len(nets._AT_END), sum(len(v[1]) for v in nets._DEFERRED.values()))
+            if Probe.own:                                    # an entry the running pass made itself, its callback queued
+                HO.queued = torch._C._current_graph_task_id()
+                HO.late.append(LateCall("event", None, None, 0))
+                HO.tail.append(TailEntry("event", None, [], None))
+            HO.submit([])                                    # (an entry point with nothing to do but its stale check)
+            Probe.seen = counts()
             return g * 2
 
-    saved = (list(nets._LATE), list(nets._AT_END), nets._CALLBACK_QUEUED[0])
     try:
-        nets._LATE.append(("event", None, None, None, 0))
-        nets._AT_END.append(("event", None, []))
-        nets._DEFERRED[-1] = (None, ["item"])
-        nets._CALLBACK_QUEUED[0] = -12345                      # a pass whose callback never ran
+        HO.late.append(LateCall("event", None, None, 0))
+        HO.at_end.append(Batch("event", None, None, []))
+        HO.deferred[-1] = Held(None, ["item"])
+        HO.inline_bias[-1] = Held(None, ["sum"])
+        HO.tail.append(TailEntry("event", None, ["item"], None))
+        HO.tail_sink, HO.encoder_end = ["item"], True
+        HO.queued = -12345                                   # a pass whose callback never ran
+        Probe.own = False
         x = torch.ones(3, requires_grad=True)
         Probe.apply(x).sum().backward()
-        assert Probe.seen == (0, 0, 0)
-        # ... while the running pass's own entries stay
-        nets._LATE.append(("event", None, None, None, 0))
-        nets._CALLBACK_QUEUED[0] = None
+        assert Probe.seen == (0, 0, 0, 0, None, False, 0)
+        assert HO.queued is None
+        # ... while the running pass's own entries stay: with nothing queued,
+        HO.late.append(LateCall("event", None, None, 0))
+        HO.tail.append(TailEntry("event", None, [], None))
+        HO.queued = None
         Probe.apply(x).sum().backward()
-        assert Probe.seen[0] == 1
+        assert Probe.seen[0] == 1 and Probe.seen[3] == 1
+        # ... and with the pass's own callback queued
+        HO._reset_pass()
+        Probe.own = True
+        Probe.apply(x).sum().backward()
+        assert Probe.seen[0] == 1 and Probe.seen[3] == 1
     finally:
-        nets._DEFERRED.pop(-1, None)
-        nets._LATE[:] = saved[0]
-        nets._AT_END[:] = saved[1]
-        nets._CALLBACK_QUEUED[0] = saved[2]
+        HO.deferred.pop(-1, None)
+        HO.inline_bias.pop(-1, None)
+        HO._reset_pass()

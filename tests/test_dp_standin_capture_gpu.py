@@ -6,7 +6,7 @@ two processes share the GPU, a stand-in for rccl_direct.DirectComm multiplies by
 the same values, as both ranks step on the same batch — and every step is captured and replayed.  A bucket reduced too early
 scales an incomplete gradient and leaves what lands later unscaled; a SyncBN exchange at the wrong place scales the wrong sums.
 Inside a capture every hand-over — weight-gradient batches, bucket reductions — is issued at the end of the backward pass behind
-events (nets.flush_deferred / late_call, DataParallelContext._reduce_range): this is the test of those dependencies, for each
+events (HO.flush_deferred / late_call, DataParallelContext._reduce_range): this is the test of those dependencies, for each
 placement of the weight gradients and both encoder arrangements, against one process stepping without data parallelism."""
 import os
 import socket
@@ -86,7 +86,7 @@ def _rank_main(rank, world, port, out_path, lanes, wgrad):
     dev = torch.device("cuda", 0)
     dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
     try:
-        from fsnet_amd.engine import nets
+        from fsnet_amd.engine.handover import HO
         from fsnet_amd.engine.dataparallel import DataParallelContext
         from fsnet_amd.engine.runtime import RT
         m, opt, hook = _build(dev, lanes)
@@ -95,13 +95,13 @@ def _rank_main(rank, world, port, out_path, lanes, wgrad):
         RT.dp = DataParallelContext(m)
         fake = _StandInComm(dev, world)
         RT.dp._direct, RT.dp._comm_stream, RT.dp.capturable = fake, RT.new_stream(dev), True
-        before = dict(nets.HANDOVERS)
+        before = dict(HO.counts)
         losses, params, grads = _steps(hook, m, opt)
         assert hook.graph_captures == 1 and hook.graph_replays == STEPS - 3, (hook.graph_captures, hook.graph_replays)
         assert RT.dp.wgrad_mode == wgrad and bool(RT.lanes) == lanes
         if wgrad == "companion":
-            assert nets.HANDOVERS["late"] > before["late"]          # (batches put off inside the capture)
-        assert not nets._LATE and not nets._AT_END
+            assert HO.counts["late"] > before["late"]          # (batches put off inside the capture)
+        assert not HO.late and not HO.at_end
         calls = fake.calls
         RT.dp._direct = None                                        # (nothing to close: the stand-in owns no communicator)
         RT.dp.close()

@@ -84,13 +84,13 @@ def test_graph_falls_back_on_new_batch_shape(dev):
 @pytest.mark.parametrize("arch", ["two equal chains", "resnet34 + resnet18", "one chain"])
 def test_replayed_step_leaves_every_parameter_gradient(dev, arch):
     """Inside a capture the weight-gradient batches are issued late, and with two equal chains partly on the pose chain's
-    streams (nets.flush_deferred): every parameter's gradient after the first replayed step is the eager step's (a batch
+    streams (HO.flush_deferred): every parameter's gradient after the first replayed step is the eager step's (a batch
     dropped or issued against the wrong event leaves zeros or garbage in ITS layers only — relative error 1 or more — and
     the loss and parameter comparisons above have tolerances a few layers can hide in.  Two EAGER runs of this step differ
     by up to 4e-2 in single encoder layers, tools/probes/grad_late.py: per-pixel minima that flip with the summation order
     of the step before)."""
     from fsnet_amd.configs import meta_arch_cfg, training_cfg
-    from fsnet_amd.engine import nets
+    from fsnet_amd.engine.handover import HO
     from tests.helpers_scene import corridor_batch
     from fsnet_amd.engine.runtime import RT
     from fsnet_amd.vision_base.networks.optimizers.optimizers import build_optimizer
@@ -112,16 +112,16 @@ def test_replayed_step_leaves_every_parameter_gradient(dev, arch):
             tc = training_cfg()
             opt = build_optimizer(m, **tc.optimizer)
             hook = build(use_graph=use_graph, graph_warmup=2, **tc.training_hook)
-            before = dict(nets.HANDOVERS)
+            before = dict(HO.counts)
             for it in range(3):                        # two eager steps, then the captured step's first replay
                 hook(dict(corridor_batch(B, H, W, seed=90 + it, device=dev)[0]), m, opt)
             torch.cuda.synchronize()
             assert hook.graph_captures == (1 if use_graph else 0)
             grads[use_graph] = {k: p.grad.detach().double().cpu() for k, p in m.named_parameters() if p.grad is not None}
             if use_graph:
-                assert nets.HANDOVERS["late"] > before["late"]
-                assert (nets.HANDOVERS["shared"] > before["shared"]) == (arch == "two equal chains")
-                assert not nets._LATE and not nets._AT_END
+                assert HO.counts["late"] > before["late"]
+                assert (HO.counts["shared"] > before["shared"]) == (arch == "two equal chains")
+                assert not HO.late and not HO.at_end
     finally:
         RT.set_compute_dtype(torch.bfloat16)
     gmax = max(float(g.norm()) for g in grads[False].values())

@@ -623,8 +623,8 @@ def test_frozen_stages_and_norm_eval_training_steps(dev, fs, ne):
         res = m(dict((k, v.to(dev) if torch.is_tensor(v) else v) for k, v in O.synthetic_batch(2, 64, 128, seed=299).items()),
                 dict(is_training=True))
         res["loss"].mean().backward()
-        from fsnet_amd.engine.nets import join_companions_final
-        join_companions_final()
+        from fsnet_amd.engine.handover import HO
+        HO.join_companions_final()
         torch.cuda.synchronize()
         top = max(float(g.norm()) for g in raw.values())
         for k, p in m.named_parameters():

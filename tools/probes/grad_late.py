@@ -3,7 +3,6 @@ import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", ".."))
 import torch
 from fsnet_amd.configs import meta_arch_cfg, training_cfg
-from fsnet_amd.engine import nets
 from fsnet_amd.engine.runtime import RT
 from fsnet_amd.vision_base.networks.optimizers.optimizers import build_optimizer
 from fsnet_amd.vision_base.utils.builder import build

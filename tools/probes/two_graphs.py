@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import torch
 import bench
 from fsnet_amd.configs import meta_arch_cfg, training_cfg
-from fsnet_amd.engine.nets import join_companions_final
+from fsnet_amd.engine.handover import HO
 from fsnet_amd.engine.runtime import RT
 from fsnet_amd.vision_base.networks.optimizers.optimizers import build_optimizer
 from fsnet_amd.vision_base.utils.builder import build
@@ -55,10 +55,10 @@ gT, gdd = grads[:2], grads[2:]
 keep = [(t, g) for t, g in zip(dd, gdd) if g is not None]
 with torch.cuda.graph(gB, stream=main):
     torch.autograd.backward([t for t, _ in keep], [g for _, g in keep])
-    join_companions_final()
+    HO.join_companions_final()
 with torch.cuda.graph(gC, stream=side):
     torch.autograd.backward(list(Ts), list(gT))
-    join_companions_final()
+    HO.join_companions_final()
 steps_before = opt._step_count_fused
 with torch.cuda.graph(gD, stream=main):
     opt.step(max_norm=35.0, grad_scale=1.0)
