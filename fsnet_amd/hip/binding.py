@@ -201,6 +201,15 @@ class FsMotionMaskArgs(C.Structure):
     ]
 
 
+class FsDistillUnscaledArgs(C.Structure):
+    _fields_ = [
+        ("pred", C.c_void_p * 4), ("teacher", C.c_void_p * 4), ("uncertain", C.c_void_p * 4),
+        ("d_pred", C.c_void_p * 4), ("d_uncertain", C.c_void_p * 4),
+        ("workspace", C.c_void_p), ("loss_out", C.c_void_p), ("gout", C.c_void_p),
+        ("n", C.c_int64 * 4), ("planes", C.c_int32), ("S", C.c_int32),
+    ]
+
+
 ABI_VERSION = 15    # FS_ABI_VERSION of include/fsnet_hip.h (tests/test_abi.py holds the two together)
 _lib = None
 

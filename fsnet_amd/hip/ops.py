@@ -5,8 +5,8 @@ import os
 
 import torch
 
-from .binding import (lib, check, stream_ptr, FsBnApplyArgs, FsBnBwdArgs, FsFlowArgs, FsMotionMaskArgs, FsPhotoArgs,
-                      FsPhotoMultiArgs, FsPostOptArgs, FsSmoothArgs)
+from .binding import (lib, check, stream_ptr, FsBnApplyArgs, FsBnBwdArgs, FsDistillUnscaledArgs, FsFlowArgs,
+                      FsMotionMaskArgs, FsPhotoArgs, FsPhotoMultiArgs, FsPostOptArgs, FsSmoothArgs)
 from .conv import dtype_code, _timed, BN_EPS, BN_MOMENTUM, Spec, run_specs
 
 STAT_SLOTS = 8   # FS_STAT_SLOTS in include/fsnet_hip.h
@@ -1260,6 +1260,61 @@ def distill_bwd(pred, teacher, uncertain, gout):
     d_unc = torch.empty_like(uncertain) if uncertain is not None else None
     check(lib.fs_distill_bwd(pred.data_ptr(), teacher.data_ptr(), _p(uncertain), pred.numel(), _p(gout), d_pred.data_ptr(),
                              _p(d_unc), stream_ptr()), "distill_bwd")
+    return d_pred, d_unc
+
+
+def distill_unscaled_chunk():
+    """elements of a plane that one block of the scale-aligned distillation kernels covers"""
+    return int(lib.fs_distill_unscaled_chunk())
+
+
+def distill_unscaled_fwd(preds, teachers, uncertains=None):
+    """is_unscaled_distill: per (sample, channel) plane ratio = mean(pred / (teacher + 1e-5)), then the mean over all
+    elements of |ratio * teacher - pred| (/ uncertain + log(uncertain + 1e-5)), for 1..4 scales in one call.
+    preds, teachers (and uncertains): lists of fp32 [B,C,h_s,w_s] with one B*C.
+    -> (f64 [S] losses on the device, context for distill_unscaled_bwd).  No host sync."""
+    S = len(preds)
+    assert 1 <= S <= 4 and len(teachers) == S and (uncertains is None or len(uncertains) == S)
+    planes = preds[0].shape[0] * preds[0].shape[1]
+    a = FsDistillUnscaledArgs()
+    keep = []
+    for s in range(S):
+        p, t = preds[s], teachers[s]
+        assert p.dim() == 4 and p.shape == t.shape and p.dtype == t.dtype == torch.float32
+        assert p.shape[0] * p.shape[1] == planes, "every scale has the same number of planes"
+        p, t = p.contiguous(), t.contiguous()
+        a.pred[s], a.teacher[s], a.n[s] = p.data_ptr(), t.data_ptr(), p.shape[2] * p.shape[3]
+        keep += [p, t]
+        if uncertains is not None:
+            u = uncertains[s]
+            assert u.shape == p.shape and u.dtype == torch.float32
+            u = u.contiguous()
+            a.uncertain[s] = u.data_ptr()
+            keep.append(u)
+    a.planes, a.S = planes, S
+    nbytes = int(lib.fs_distill_unscaled_workspace_bytes(planes, C.addressof(a.n), S))
+    if nbytes < 0:
+        check(1, "distill_unscaled_workspace_bytes")
+    dev = preds[0].device
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    losses = torch.empty(S, dtype=torch.float64, device=dev)
+    a.workspace, a.loss_out = ws.data_ptr(), losses.data_ptr()
+    check(lib.fs_distill_unscaled_fwd(C.byref(a), stream_ptr()), "distill_unscaled_fwd")
+    return losses, (a, keep, ws, [preds[s].shape for s in range(S)], uncertains is not None, dev)
+
+
+def distill_unscaled_bwd(ctx, gouts=None):
+    """gouts: f64 [S] on the device (None: ones) -> (d_pred[s], d_uncertain[s] or None), fresh tensors"""
+    a, keep, ws, shapes, unc, dev = ctx
+    d_pred = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes]
+    d_unc = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes] if unc else None
+    if gouts is not None:
+        assert gouts.dtype == torch.float64 and gouts.numel() == a.S and gouts.is_contiguous()
+    for s in range(a.S):
+        a.d_pred[s] = d_pred[s].data_ptr()
+        a.d_uncertain[s] = d_unc[s].data_ptr() if unc else None
+    a.gout = _p(gouts)
+    check(lib.fs_distill_unscaled_bwd(C.byref(a), stream_ptr()), "distill_unscaled_bwd")
     return d_pred, d_unc
 
 

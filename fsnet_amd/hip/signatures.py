@@ -39,7 +39,12 @@ SIGNATURES = {
     "fs_sigmoid_head_bwd": (C.c_int, [P, P, P, L, I, I, P]),
     "fs_distill_fwd": (C.c_int, [P, P, P, L, P, P]),
     "fs_distill_bwd": (C.c_int, [P, P, P, L, P, P, P, P]),
-    "fs_resize_linear": (C.c_int, [P, P, I, I, I, I, I, P]),
+    # added under ABI 15: is_unscaled_distill over 1..4 scales (FsDistillUnscaledArgs)
+    "fs_distill_unscaled_fwd": (C.c_int, [P, P]),
+    "fs_distill_unscaled_bwd": (C.c_int, [P, P]),
+    "fs_distill_unscaled_workspace_bytes": (C.c_int64, [I, P, I]),
+    "fs_distill_unscaled_chunk": (C.c_int, []),
+    "fs_resize_linear":(C.c_int, [P, P, I, I, I, I, I, P]),
     "fs_depth_eval": (C.c_int, [P, P, I, I, I, I, I, P, P, P]),
     # ABI 14: Kitti360FisheyeEvaluator._single_loss (kitti360_fisheye_eval.py:43-72) and _precompute (:97-145)
     "fs_depth_eval_masked": (C.c_int, [P, P, P, I, I, I, I, I, F, F, I, P, P, P]),

@@ -60,6 +60,26 @@ class _DistillFn(torch.autograd.Function):
         return d_pred, None, d_unc
 
 
+class _DistillUnscaledFn(torch.autograd.Function):
+    """(S, with_unc, pred_1..S, teacher_1..S[, uncertain_1..S]) -> S scalar losses of is_unscaled_distill, every scale in
+    one set of launches; the gradient flows through each plane's ratio as well"""
+
+    @staticmethod
+    def forward(ctx, S, with_unc, *rest):
+        preds = [t.contiguous().float() for t in rest[:S]]
+        teachers = [t.contiguous().float() for t in rest[S:2 * S]]
+        uncs = [t.contiguous().float() for t in rest[2 * S:3 * S]] if with_unc else None
+        losses, ctx.du = ops.distill_unscaled_fwd(preds, teachers, uncs)
+        ctx.S, ctx.with_unc = S, with_unc
+        return tuple(losses.unbind(0))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        gouts = torch.stack([g.detach().double() for g in gs])
+        d_pred, d_unc = ops.distill_unscaled_bwd(ctx.du, gouts)
+        return (None, None) + tuple(d_pred) + (None,) * ctx.S + (tuple(d_unc) if ctx.with_unc else ())
+
+
 class MonoDepth2Decoder(nn.Module):
     def __init__(self, scales, height, width, frame_ids, depth_decoder_cfg, pose_decoder_cfg=None,
                  multiscale_head_cfg=None, **kwargs):
@@ -102,8 +122,6 @@ class MonoDepth2Decoder(nn.Module):
                 raise NotImplementedError("MonoDepth2Decoder option %s is not implemented in the HIP loss chain" % flag)
         if getattr(self, "residualflow_weight", 0) > 0:
             raise NotImplementedError("MonoDepth2Decoder term residualflow_weight > 0 is not implemented in the HIP loss chain")
-        if getattr(self, "distillation_loss_weight", 0) > 0 and getattr(self, "is_unscaled_distill", False):
-            raise NotImplementedError("is_unscaled_distill=True is not implemented (no shipped config enables it)")
         self._check_frame_ids()
 
     MAX_SOURCES = 4
@@ -237,11 +255,22 @@ class MonoDepth2Decoder(nn.Module):
         return pose_loss
 
     def compute_distill_loss(self, output_dict, input_dict, scale):
-        """monodepth2_decoder.py:185-203: mean |teacher - pred| (/ uncertain_z + log(uncertain_z + 1e-5))"""
+        """monodepth2_decoder.py:185-203: mean |teacher - pred| (/ uncertain_z + log(uncertain_z + 1e-5)); with
+        is_unscaled_distill the teacher is first scaled by each sample's mean of pred / (teacher + 1e-5)"""
+        if getattr(self, 'is_unscaled_distill', False):
+            return self._distill_unscaled(output_dict, [scale])[0]
         pred = output_dict[('depth', scale, scale)]
         teacher = output_dict[('teacher_depth', scale, scale)].detach()
         unc = output_dict[('uncertain_z', scale)] if getattr(self, 'is_uncertain_distill', False) else None
         return _DistillFn.apply(pred, teacher, unc)
+
+    def _distill_unscaled(self, output_dict, scales):
+        """the is_unscaled_distill term of every scale in `scales` from one set of launches"""
+        with_unc = bool(getattr(self, 'is_uncertain_distill', False))
+        preds = [output_dict[('depth', s, s)] for s in scales]
+        teachers = [output_dict[('teacher_depth', s, s)].detach() for s in scales]
+        uncs = [output_dict[('uncertain_z', s)] for s in scales] if with_unc else []
+        return _DistillUnscaledFn.apply(len(scales), with_unc, *preds, *teachers, *uncs)
 
     def loss(self, output_dict, input_dict):
         losses, hm, total = self.compute_total_reprojection_loss(output_dict, input_dict)
@@ -252,8 +281,11 @@ class MonoDepth2Decoder(nn.Module):
             total = total + pose_weight * pose_loss
         distillation_weight = getattr(self, 'distillation_loss_weight', 0)
         if distillation_weight > 0:                                   # reference :328-334
-            for scale in self.scales:
-                dl = self.compute_distill_loss(output_dict, input_dict, scale)
+            if getattr(self, 'is_unscaled_distill', False):
+                dls = self._distill_unscaled(output_dict, self.scales)
+            else:
+                dls = [self.compute_distill_loss(output_dict, input_dict, scale) for scale in self.scales]
+            for scale, dl in zip(self.scales, dls):
                 losses["distilation/{}".format(scale)] = dl.detach()
                 total = total + dl * distillation_weight
         losses["total_loss"] = total.detach()

@@ -285,6 +285,40 @@ int fs_distill_fwd(const float* pred, const float* teacher, const float* uncerta
 int fs_distill_bwd(const float* pred, const float* teacher, const float* uncertain, int64_t n, const double* gout,
                    float* d_pred, float* d_uncertain, void* stream);
 
+/* Scale-aligned distillation (monodepth2_decoder.py:185-203, is_unscaled_distill = True), one to four scales per
+ * launch.  Tensors are fp32 [planes][n[s]]; a plane is one (sample, channel) of n = h*w elements.  Per plane
+ *   ratio = mean_j p_j / (t_j + 1e-5)   (f64 sum of the fp32 quotients, rounded to fp32 once)
+ *   x_i = ratio t_i - p_i (fp32, never fused),  term_i = |x_i| / u_i + log(u_i + 1e-5)   (uncertain NULL: |x_i|)
+ *   loss_out[s] = mean of term_i over all planes * n[s] elements
+ * and, with k = gout[s] / (planes n[s]) (gout NULL: 1), w = 1 / u (or 1), s = sign(x) (0 at 0), G = sum_plane w s t:
+ *   d_pred_i = k (-w_i s_i + (G / n) / (t_i + 1e-5)),   d_uncertain_i = k (-|x_i| / u_i^2 + 1 / (u_i + 1e-5)).
+ * fs_distill_unscaled_fwd: a ratio pass, a loss pass and a one-block sum, which leave per-block f64 partials
+ * [plane][chunk] in the workspace; fs_distill_unscaled_bwd: one pass that reads them, so it follows a forward with the
+ * same pred / teacher / uncertain / workspace.  Sums have one fixed order and no floating-point atomics: equal inputs
+ * give equal bits, whatever the alignment of the planes (n may be odd; 16-byte accesses only where the address allows).
+ * uncertain[0..S): all NULL or all set, d_uncertain likewise and set exactly when uncertain is; the forward needs
+ * loss_out, the backward d_pred.  FS_EINVAL, before anything is launched: a needed pointer NULL, S outside 1..4,
+ * planes < 1, an n[s] < 1, a half-set uncertain / d_uncertain, planes * chunks >= 2^31.  No host sync: capturable.
+ * fs_distill_unscaled_workspace_bytes: size of the workspace for (planes, n[0..S), S), -1 where the main calls refuse.
+ * fs_distill_unscaled_chunk: elements of a plane that one block covers. */
+typedef struct FsDistillUnscaledArgs {
+  const float* pred[4];
+  const float* teacher[4];
+  const float* uncertain[4];
+  float* d_pred[4];
+  float* d_uncertain[4];
+  void* workspace;
+  double* loss_out;       /* f64 [S] */
+  const double* gout;     /* f64 [S], or NULL */
+  int64_t n[4];
+  int32_t planes;
+  int32_t S;
+} FsDistillUnscaledArgs;
+int fs_distill_unscaled_fwd(const FsDistillUnscaledArgs* args, void* stream);
+int fs_distill_unscaled_bwd(const FsDistillUnscaledArgs* args, void* stream);
+int64_t fs_distill_unscaled_workspace_bytes(int planes, const int64_t* n, int S);
+int fs_distill_unscaled_chunk(void);
+
 /* Training input pipeline: raw uint8 frames -> network / loss inputs in one launch.  Per sample b
  * and frame f: cv2.warpAffine(INTER_LINEAR, BORDER_CONSTANT) with the inverted map minv[b] (f64, computed by the host
  * exactly as OpenCV inverts the forward matrix), RandomMirror, the colour chain in the drawn order, Normalize and the

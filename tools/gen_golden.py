@@ -318,17 +318,15 @@ def gen_eval():
     np.savez_compressed(os.path.join(GOLD, "eval.npz"), **out)
 
 
-def gen_distill():
-    """self-distillation stage through the REAL DistillWPoseMeta (monodepth2_model.py:150-206): loss terms and
-    parameter-gradient norms on a seeded batch; cross-checks oracle/distill_oracle.py"""
+def _real_distill_step(H, W, B, seed, teacher_seed, batch_seed, **head_flags):
+    """one training step of the REAL DistillWPoseMeta with its gradients -> (model, output, batch)"""
     import tempfile
     from oracle import distill_oracle as D
-    H, W, B = 64, 128, 2
     enc = dict(name='vision_base.networks.models.backbone.resnet.resnet', depth=18, pretrained=False, frozen_stages=-1,
                num_stages=4, out_indices=(-1, 0, 1, 2, 3), norm_eval=False, dilations=(1, 1, 1, 1))
     dec = dict(num_ch_enc=np.array([64, 64, 128, 256, 512]), num_output_channels=16, use_skips=True, scales=[0, 1, 2, 3],
                min_depth=0.5, max_depth=100)
-    sd = D.init_states(seed=21, teacher_seed=22)
+    sd = D.init_states(seed=seed, teacher_seed=teacher_seed)
     with tempfile.TemporaryDirectory() as d:
         tpath = os.path.join(d, "teacher.pth")
         torch.save({k[len("teacher_net."):]: v.clone() for k, v in sd.items() if k.startswith("teacher_net.")}, tpath)
@@ -341,15 +339,24 @@ def gen_distill():
                   head_cfg=EasyDict(name='monodepth.networks.models.heads.monodepth2_decoder.MonoDepth2Decoder',
                                     scales=[0, 1, 2, 3], height=H, width=W, min_depth=0.5, max_depth=100.0,
                                     overlapped_mask=True, is_log_image=False, distillation_loss_weight=0.3,
-                                    is_uncertain_distill=True,
-                                    depth_decoder_cfg=EasyDict(name='monodepth.networks.models.heads.depth_encoder.MultiChannelDepthDecoderUncertain', **dec)),
+                                    depth_decoder_cfg=EasyDict(name='monodepth.networks.models.heads.depth_encoder.MultiChannelDepthDecoderUncertain', **dec),
+                                    **dict(dict(is_uncertain_distill=True), **head_flags)),
                   train_cfg=EasyDict(frame_ids=[0, 1, -1]), test_cfg=EasyDict())
     m.load_state_dict({k: v.clone() for k, v in sd.items()}, strict=True)
     m.train()
-    data = O.synthetic_batch(B, H, W, seed=400)
+    data = O.synthetic_batch(B, H, W, seed=batch_seed)
     torch.manual_seed(0)
     out = m(dict(data), dict(is_training=True, epoch_num=0, global_step=0))
     out["loss"].backward()
+    return m, out, data
+
+
+def gen_distill():
+    """self-distillation stage through the REAL DistillWPoseMeta (monodepth2_model.py:150-206): loss terms and
+    parameter-gradient norms on a seeded batch; cross-checks oracle/distill_oracle.py"""
+    from oracle import distill_oracle as D
+    H, W, B = 64, 128, 2
+    m, out, data = _real_distill_step(H, W, B, 21, 22, 400)
     names = [k for k, _ in m.named_parameters() if not k.startswith("teacher_net.")]
     gn = np.array([float(p.grad.norm()) if p.grad is not None else 0.0 for k, p in m.named_parameters()
                    if not k.startswith("teacher_net.")])
@@ -373,6 +380,61 @@ def gen_distill():
         if k.startswith("distilation"):
             print("   %s ref %.6f oracle %.6f" % (k, res["ld_" + k.replace("/", "_")], float(losses[k])))
     np.savez_compressed(os.path.join(GOLD, "distill.npz"), **res)
+
+
+def gen_distill_unscaled():
+    """is_unscaled_distill (monodepth2_decoder.py:185-203): the REAL compute_distill_loss on the small cases of
+    tests/helpers_distill_unscaled.py with gradients, with and without is_uncertain_distill, and the REAL DistillWPoseMeta
+    step of gen_distill with the flag set; cross-checks the helper's restatement and its oracle step.  Layout of the
+    file: helpers_distill_unscaled.golden_rows() / digest()"""
+    from tests import helpers_distill_unscaled as HU
+    from oracle import distill_oracle as D
+    head = ref_model(64, 128, with_pose=False).head
+    head.is_unscaled_distill = True
+    rows = HU.golden_rows()
+    k_loss = np.zeros([len(rows), 2], np.float32)
+    k_grad = np.zeros([len(rows), 2, 2, HU.SAMPLES + 2], np.float32)      # [row][with_unc][d_pred, d_uncertain][digest]
+    worst = 0.0
+    for r, (name, s) in enumerate(rows):
+        c = HU.case(name)
+        for unc in (0, 1):
+            head.is_uncertain_distill = bool(unc)
+            p = c["pred"][s].clone().requires_grad_(True)
+            u = c["uncertain"][s].clone().requires_grad_(True)
+            od = {("depth", 7, 7): p, ("teacher_depth", 7, 7): c["teacher"][s].clone(), ("uncertain_z", 7): u}
+            loss = head.compute_distill_loss(od, {}, 7)
+            loss.backward()
+            k_loss[r, unc] = float(loss.detach())
+            k_grad[r, unc, 0] = HU.digest(p.grad)
+            if unc:
+                k_grad[r, unc, 1] = HU.digest(u.grad)
+            mine = HU.restate(c["pred"][s], c["teacher"][s], c["uncertain"][s] if unc else None)
+            worst = max(worst, dev(mine[0], loss.detach()), dev(mine[1], p.grad) / float(p.grad.abs().max()))
+    print("distill_unscaled: restatement vs the real method, worst deviation %.3e" % worst)
+    M = HU.MODEL
+    m_loss = np.zeros([2, 5], np.float32)                                   # [with_unc][total, distilation/0..3]
+    m_gradnorm = []
+    for unc in (0, 1):
+        m, out, data = _real_distill_step(M["H"], M["W"], M["B"], M["seed"], M["teacher_seed"], M["batch_seed"],
+                                          is_unscaled_distill=True, is_uncertain_distill=bool(unc))
+        names = [k for k, _ in m.named_parameters() if not k.startswith("teacher_net.")]
+        m_gradnorm.append([float(p.grad.norm()) if p.grad is not None else 0.0 for k, p in m.named_parameters()
+                           if not k.startswith("teacher_net.")])
+        m_loss[unc] = [float(out["loss"].detach())] + [float(out["loss_dict"]["distilation/%d" % s]) for s in range(4)]
+        sdo = D.init_states(seed=M["seed"], teacher_seed=M["teacher_seed"])
+        for k in sdo:
+            if D.is_student_param(k):
+                sdo[k].requires_grad_(True)
+        tot, losses, _ = HU.forward_train_unscaled(sdo, O.synthetic_batch(M["B"], M["H"], M["W"], seed=M["batch_seed"]),
+                                                   is_uncertain_distill=bool(unc))
+        tot.backward()
+        gno = np.array([float(sdo[k].grad.norm()) if sdo[k].grad is not None else 0.0 for k in names])
+        gn = np.array(m_gradnorm[-1])
+        print("distill_unscaled[unc=%d]: loss ref %.8f oracle %.8f | gradnorm max rel dev %.3e | distilation/0 ref %.6f "
+              "oracle %.6f" % (unc, m_loss[unc, 0], float(tot.detach()), np.abs(gno - gn).max() / gn.max(), m_loss[unc, 1],
+                               float(losses["distilation/0"])))
+    np.savez_compressed(os.path.join(GOLD, "distill_unscaled.npz"), k_seed=np.array([HU.case(n)["seed"] for n in HU.SMALL], np.int32),
+                        k_loss=k_loss, k_grad=k_grad, m_loss=m_loss, m_gradnorm=np.array(m_gradnorm, np.float32))
 
 
 def gen_augment():
@@ -1587,6 +1649,9 @@ if __name__ == "__main__":
     if "--only-sigmoid" in sys.argv:
         gen_sigmoid_decoder()
         sys.exit(0)
+    if "--only-distill-unscaled" in sys.argv:
+        gen_distill_unscaled()
+        sys.exit(0)
     if "--only-teacher" in sys.argv:
         gen_teacher_keys()
         sys.exit(0)
@@ -1633,6 +1698,7 @@ if __name__ == "__main__":
     gen_model(False, "wpose")
     gen_eval()
     gen_distill()
+    gen_distill_unscaled()
     gen_augment()
     gen_fisheye()
     gen_model_r50fx()
