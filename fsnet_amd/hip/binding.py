@@ -210,6 +210,21 @@ class FsDistillUnscaledArgs(C.Structure):
     ]
 
 
+class FsDcnArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("offset", C.c_void_p), ("mask", C.c_void_p), ("w_f", C.c_void_p), ("w_d", C.c_void_p),
+        ("bias", C.c_void_p), ("out", C.c_void_p), ("dy", C.c_void_p), ("dx", C.c_void_p),
+        ("d_offset", C.c_void_p), ("d_mask", C.c_void_p), ("dw", C.c_void_p), ("d_bias", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+        ("w_f_row", C.c_int64), ("w_d_row", C.c_int64),
+        ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32),
+        ("Ci", C.c_int32), ("Ci_p", C.c_int32), ("Co", C.c_int32), ("Co_p", C.c_int32), ("R", C.c_int32), ("S", C.c_int32),
+        ("stride_h", C.c_int32), ("stride_w", C.c_int32), ("pad_h", C.c_int32), ("pad_w", C.c_int32),
+        ("dil_h", C.c_int32), ("dil_w", C.c_int32),
+        ("groups", C.c_int32), ("deformable_groups", C.c_int32),
+    ]
+
+
 ABI_VERSION = 15    # FS_ABI_VERSION of include/fsnet_hip.h (tests/test_abi.py holds the two together)
 _lib = None
 

@@ -4,10 +4,11 @@ import ctypes as C
 import os
 
 import torch
+from torch.nn.modules.utils import _pair
 
-from .binding import (lib, check, stream_ptr, FsBnApplyArgs, FsBnBwdArgs, FsDistillUnscaledArgs, FsFlowArgs,
+from .binding import (lib, check, stream_ptr, FsBnApplyArgs, FsBnBwdArgs, FsDcnArgs, FsDistillUnscaledArgs, FsFlowArgs,
                       FsMotionMaskArgs, FsPhotoArgs, FsPhotoMultiArgs, FsPostOptArgs, FsSmoothArgs)
-from .conv import dtype_code, _timed, BN_EPS, BN_MOMENTUM, Spec, run_specs
+from .conv import dtype_code, roundup, _timed, BN_EPS, BN_MOMENTUM, Spec, run_specs
 
 STAT_SLOTS = 8   # FS_STAT_SLOTS in include/fsnet_hip.h
 
@@ -1362,3 +1363,137 @@ def cost_volume(cur, look, K, inv_K, poses, bins, cat, want_volume=False):
     if want_volume:
         return conf, lowest, vol, miss
     return conf, lowest
+
+
+# ---------------------------------------------------------------------------------- deformable convolution (dcn.hip)
+def dcn_tile(which):
+    """(pixels, channels) one block owns: which = 0 forward, 1 data backward, 2 weight gradient (fs_dcn_tile)"""
+    px, ch = C.c_int32(), C.c_int32()
+    check(lib.fs_dcn_tile(which, C.byref(px), C.byref(ch)), "dcn_tile")
+    return px.value, ch.value
+
+
+DCN_MAX_PAD = DCN_MAX_DIL = 64          # what check_geometry of dcn.hip takes
+
+
+class DcnGeometry:
+    """Shapes and options of one deformable convolution (deform_conv.py:54-223).  What the kernels do not take raises
+    NotImplementedError naming the option — on any device, before anything is launched."""
+
+    def __init__(self, in_shape, w_shape, stride, padding, dilation, groups, deformable_groups, dtype):
+        self.N, self.Ci, self.H, self.W = (int(v) for v in in_shape)
+        self.Co, ci_w, self.R, self.S = (int(v) for v in w_shape)
+        self.stride, self.padding, self.dilation = (tuple(int(v) for v in _pair(o)) for o in (stride, padding, dilation))
+        self.groups, self.dg = int(groups), int(deformable_groups)
+        self.dtype, self.code = dtype, dtype_code(dtype)
+        self.EG = 8 if dtype == torch.bfloat16 else 4
+        if self.groups != 1:
+            raise NotImplementedError("deformable convolution: groups=%d is not supported (groups must be 1)" % self.groups)
+        if self.R > 3 or self.S > 3:
+            raise NotImplementedError("deformable convolution: kernel_size=%dx%d is not supported (at most 3x3)" % (self.R, self.S))
+        if any(s not in (1, 2) for s in self.stride):
+            raise NotImplementedError("deformable convolution: stride=%s is not supported (1 or 2)" % (self.stride,))
+        if any(not 0 <= v <= DCN_MAX_PAD for v in self.padding):
+            raise NotImplementedError("deformable convolution: padding=%s is not supported (0 .. %d)" % (self.padding, DCN_MAX_PAD))
+        if any(not 1 <= v <= DCN_MAX_DIL for v in self.dilation):
+            raise NotImplementedError("deformable convolution: dilation=%s is not supported (1 .. %d)" % (self.dilation, DCN_MAX_DIL))
+        if ci_w != self.Ci:
+            raise ValueError("deformable convolution: weight expects %d input channels, input has %d" % (ci_w, self.Ci))
+        if self.dg < 1 or self.Ci % self.dg:
+            raise ValueError("deformable convolution: deformable_groups=%d does not divide %d channels" % (self.dg, self.Ci))
+        if self.dg > 1 and (self.Ci // self.dg) % self.EG:
+            raise NotImplementedError("deformable convolution: deformable_groups=%d leaves %d channels per group, not a "
+                                      "multiple of %d (whole 16-byte units)" % (self.dg, self.Ci // self.dg, self.EG))
+        self.Ci_p, self.Co_p = roundup(self.Ci, self.EG), roundup(self.Co, 16)
+        ext = [(i + 2 * p - (d * (k - 1) + 1)) // s + 1 for i, p, d, k, s in
+               zip((self.H, self.W), self.padding, self.dilation, (self.R, self.S), self.stride)]
+        if min(ext) < 1:
+            raise ValueError("convolution input is too small (output would be %dx%d)" % tuple(ext))
+        self.Ho, self.Wo = ext
+        self.RS = self.R * self.S
+
+    def args(self):
+        a = FsDcnArgs()
+        a.N, a.H, a.W, a.Ho, a.Wo = self.N, self.H, self.W, self.Ho, self.Wo
+        a.Ci, a.Ci_p, a.Co, a.Co_p, a.R, a.S = self.Ci, self.Ci_p, self.Co, self.Co_p, self.R, self.S
+        a.stride_h, a.stride_w = self.stride
+        a.pad_h, a.pad_w = self.padding
+        a.dil_h, a.dil_w = self.dilation
+        a.groups, a.deformable_groups = self.groups, self.dg
+        return a
+
+    def forward_channels(self):
+        """output channels one forward block owns for this geometry (fs_dcn_fwd_channels)"""
+        a = self.args()
+        return int(lib.fs_dcn_fwd_channels(C.byref(a), self.code))
+
+    def check_offset(self, offset, mask):
+        want = (self.N, self.dg * 2 * self.RS, self.Ho, self.Wo)
+        if tuple(offset.shape) != want:
+            raise ValueError("deformable convolution: offset is %s, expected %s" % (tuple(offset.shape), want))
+        if mask is not None and tuple(mask.shape) != (self.N, self.dg * self.RS, self.Ho, self.Wo):
+            raise ValueError("deformable convolution: mask is %s, expected %s" % (
+                tuple(mask.shape), (self.N, self.dg * self.RS, self.Ho, self.Wo)))
+
+
+def _dcn_common(g, x, offset, mask):
+    assert x.shape == (g.N, g.H, g.W, g.Ci_p) and x.dtype == g.dtype and x.is_contiguous()
+    assert offset.dtype == torch.float32 and offset.is_contiguous()
+    assert mask is None or (mask.dtype == torch.float32 and mask.is_contiguous())
+    a = g.args()
+    a.x, a.offset, a.mask = x.data_ptr(), offset.data_ptr(), _p(mask)
+    return a
+
+
+def dcn_pack(g, weight, transpose):
+    """fp32 OIHW master -> the forward operand [Co_p][R*S*Ci_p] (transpose = 0) or the data-gradient operand
+    [roundup(Ci_p, 16)][R*S*Co_p] (transpose = 1) in the compute dtype (fs_pack_weights)"""
+    w = weight.detach().float().contiguous()
+    rows, cs = (roundup(g.Ci_p, 16), g.Co_p) if transpose else (g.Co_p, g.Ci_p)
+    dst = torch.empty(rows, g.RS * cs, dtype=g.dtype, device=w.device)
+    check(lib.fs_pack_weights(w.data_ptr(), dst.data_ptr(), g.Co, g.Ci, g.R, g.S, rows, cs, g.RS * cs, int(transpose),
+                              g.code, stream_ptr()), "pack_weights")
+    return dst
+
+
+def dcn_forward(g, x, offset, mask, w_f, bias=None, out=None):
+    """x NHWC [N,H,W,Ci_p] -> out NHWC [N,Ho,Wo,Co_p], both in the compute dtype; offset / mask fp32 planar; bias fp32 [Co]"""
+    a = _dcn_common(g, x, offset, mask)
+    if out is None:
+        out = torch.empty(g.N, g.Ho, g.Wo, g.Co_p, dtype=g.dtype, device=x.device)
+    a.w_f, a.w_f_row, a.bias, a.out = w_f.data_ptr(), w_f.shape[1], _p(bias), out.data_ptr()
+    check(lib.fs_dcn_fwd(C.byref(a), g.code, stream_ptr()), "dcn_fwd")
+    return out
+
+
+def dcn_backward_data(g, x, offset, mask, w_d, dy, dx=None, d_offset=None, d_mask=None):
+    """-> (dx fp32 NHWC [N,H,W,Ci_p], d_offset, d_mask | None); every cell of the three is written"""
+    a = _dcn_common(g, x, offset, mask)
+    assert dy.shape == (g.N, g.Ho, g.Wo, g.Co_p) and dy.dtype == g.dtype and dy.is_contiguous()
+    dev = x.device
+    dx = torch.empty(g.N, g.H, g.W, g.Ci_p, dtype=torch.float32, device=dev) if dx is None else dx
+    d_offset = torch.empty_like(offset) if d_offset is None else d_offset
+    if mask is not None and d_mask is None:
+        d_mask = torch.empty_like(mask)
+    a.w_d, a.w_d_row, a.dy = w_d.data_ptr(), w_d.shape[1], dy.data_ptr()
+    a.dx, a.d_offset, a.d_mask = dx.data_ptr(), d_offset.data_ptr(), _p(d_mask)
+    check(lib.fs_dcn_bwd_data(C.byref(a), g.code, stream_ptr()), "dcn_bwd_data")
+    return dx, d_offset, d_mask
+
+
+def dcn_backward_weight(g, x, offset, mask, dy, want_bias=False, dw=None, d_bias=None):
+    """-> (dw fp32 OIHW, d_bias fp32 [Co] | None), both in a fixed summation order"""
+    a = _dcn_common(g, x, offset, mask)
+    assert dy.shape == (g.N, g.Ho, g.Wo, g.Co_p) and dy.dtype == g.dtype and dy.is_contiguous()
+    dev = x.device
+    dw = torch.empty(g.Co, g.Ci, g.R, g.S, dtype=torch.float32, device=dev) if dw is None else dw
+    if want_bias and d_bias is None:
+        d_bias = torch.empty(g.Co, dtype=torch.float32, device=dev)
+    nbytes = int(lib.fs_dcn_workspace_bytes(C.byref(a), g.code))
+    if nbytes < 0:
+        raise ValueError("deformable convolution: the library refuses this geometry")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    a.dy, a.dw, a.d_bias = dy.data_ptr(), dw.data_ptr(), _p(d_bias)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    check(lib.fs_dcn_bwd_weight(C.byref(a), g.code, stream_ptr()), "dcn_bwd_weight")
+    return dw, d_bias

@@ -128,6 +128,13 @@ SIGNATURES = {
     # added under ABI 15: the update launch with a run table (runs, n_runs before the stream) — AdamW / Adam-L2, SGD
     "fs_adamw_step": (C.c_int, [P, P, P, P, L, F, F, F, F, F, I, I, F, P, F, P, P, P, I, P]),
     "fs_sgd_step": (C.c_int, [P, P, P, L, F, F, F, I, F, I, F, P, F, P, P, P, I, P]),
+    # added under ABI 15: deformable convolution v1 / v2 (FsDcnArgs; deform_conv.py:54-223)
+    "fs_dcn_fwd": (C.c_int, [P, I, P]),
+    "fs_dcn_bwd_data": (C.c_int, [P, I, P]),
+    "fs_dcn_bwd_weight": (C.c_int, [P, I, P]),
+    "fs_dcn_workspace_bytes": (C.c_int64, [P, I]),
+    "fs_dcn_tile": (C.c_int, [I, P, P]),
+    "fs_dcn_fwd_channels": (C.c_int, [P, I]),
 }
 
 

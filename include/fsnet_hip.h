@@ -937,6 +937,51 @@ int fs_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float
                 int nesterov, float weight_decay, int step, float max_norm, const double* sumsq, float grad_scale,
                 const int32_t* step_ptr, const float* lr_ptr, const int64_t* runs, int n_runs, void* stream);
 
+/* Added under ABI 15: deformable convolution v1 / v2 — the reference's only native code, the CUDA extension behind
+ * DeformConvFunction / ModulatedDeformConvFunction (vision_base/networks/ops/dcn/deform_conv.py:54-223; kernels
+ * src/cuda/deform_conv_cuda_kernel.cu:84-243, 280-465, 571-866), consumed by the DLA upsampler (dla_utils.py:40-54).
+ * x [N][H][W][Ci_p] and out / dy [N][Ho][Wo][Co_p] are dense NHWC in the compute dtype; offset [N][dg*2*R*S][Ho][Wo] and
+ * mask [N][dg*R*S][Ho][Wo] (NULL = v1) are fp32 and read in place; w_f [Co_p][w_f_row] (K = r, s, ci) and
+ * w_d [>= Ci_p][w_d_row] (K = r, s, co) are fs_pack_weights operands (transpose 0 / 1); bias (or NULL) is fp32 [Co].
+ * groups must be 1; R, S <= 3; stride 1 or 2; with deformable_groups > 1 the channels of a group are whole 16-byte units.
+ * Anything else, a NULL or an out-of-range argument: FS_EINVAL, nothing launched.
+ * fs_dcn_fwd: out.  fs_dcn_bwd_data: dx (fp32 [N][H][W][Ci_p], zeroed by the call, summed with float atomics), d_offset and
+ * d_mask (fp32, planar, every cell written once).  fs_dcn_bwd_weight: dw fp32 OIHW [Co][Ci][R][S] and d_bias fp32 [Co]
+ * (or NULL), both overwritten, in a fixed summation order, through
+ * `workspace` (>= fs_dcn_workspace_bytes(args, dtype); -1 for arguments fs_dcn_* would refuse).
+ * fs_dcn_tile: pixels and channels one block owns; which = 0 forward, 1 data backward, 2 weight gradient (pixels of one
+ * K stage; a slab is a whole number of them). */
+typedef struct FsDcnArgs {
+  const void* x;
+  const float* offset;
+  const float* mask;
+  const void* w_f;
+  const void* w_d;
+  const float* bias;
+  void* out;
+  const void* dy;
+  float* dx;
+  float* d_offset;
+  float* d_mask;
+  float* dw;
+  float* d_bias;
+  void* workspace;
+  int64_t workspace_bytes;
+  int64_t w_f_row, w_d_row;        /* elements per operand row */
+  int32_t N, H, W, Ho, Wo;
+  int32_t Ci, Ci_p, Co, Co_p, R, S;
+  int32_t stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
+  int32_t groups, deformable_groups;
+} FsDcnArgs;
+int fs_dcn_fwd(const FsDcnArgs* args, int dtype, void* stream);
+int fs_dcn_bwd_data(const FsDcnArgs* args, int dtype, void* stream);
+int fs_dcn_bwd_weight(const FsDcnArgs* args, int dtype, void* stream);
+int64_t fs_dcn_workspace_bytes(const FsDcnArgs* args, int dtype);
+int fs_dcn_tile(int which, int32_t* pixels, int32_t* channels);
+/* output channels one forward block owns for this geometry: fs_dcn_tile(0)'s channels, halved (down to 64) while fewer
+ * than 256 blocks would run; -1 for arguments fs_dcn_fwd would refuse */
+int fs_dcn_fwd_channels(const FsDcnArgs* args, int dtype);
+
 #ifdef __cplusplus
 }
 #endif

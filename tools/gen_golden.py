@@ -1621,7 +1621,60 @@ def gen_motion_mask():
     np.savez_compressed(os.path.join(GOLD, "motion_mask.npz"), **out)
 
 
+def gen_dla_up():
+    """The reference's REAL dla_utils classes (DLASegUpsample and everything under it) on the CPU.  Their file imports
+    ModulatedDeformConvPack from the reference's deform_conv.py, which needs a CUDA torch (line 11 compares
+    torch.version.cuda with a string) and the compiled extension: torch.version.cuda is set, a stand-in deform_conv_ext
+    module is inserted, and the module-level modulated_deform_conv is pointed at the f64 restatement of
+    tests/helpers_dcn.py.  So the wiring, the names and the initialisation are the real classes'; the arithmetic of the
+    op is the restatement's.  Stored: the f64 output, the fp32 run's output (the yardstick), and for every parameter and
+    input the f64 gradient norm and the L2 norm of the fp32 run's gradient deviation."""
+    from tests import helpers_dcn as HD
+    torch.version.cuda = torch.version.cuda or "11.0"
+    pkg = "vision_base.networks.ops.dcn"
+    sys.modules.setdefault(pkg + ".deform_conv_ext", types.ModuleType(pkg + ".deform_conv_ext"))
+    import importlib
+    dc = importlib.import_module(pkg + ".deform_conv")
+    du = importlib.import_module("vision_base.networks.models.backbone.dla_utils")
+    seen = []
+
+    def restated(x, offset, mask, weight, bias, stride, padding, dilation, groups, deformable_groups):
+        assert groups == 1
+        seen.append(float(offset.detach().abs().mean()))
+        return HD.dcn_ref(x, offset, mask, weight, bias, stride, padding, dilation, deformable_groups)
+    dc.modulated_deform_conv = restated
+
+    cfg = dict(HD.DLA_UP, input_channels=list(HD.DLA_UP["input_channels"]))
+    ref = du.DLASegUpsample(**cfg)
+    keys = list(ref.state_dict())
+    assert all(float(m.conv_offset.weight.detach().abs().max()) == 0.0 for m in ref.modules()
+               if isinstance(m, dc.ModulatedDeformConvPack))            # the reference's initialisation
+    ref.load_state_dict(HD.dla_up_state(ref), strict=True)
+    pyramid, cot = HD.dla_up_inputs()
+    out64, g64 = HD.dla_up_run(ref, pyramid, cot, torch.float64)
+    layers = len(seen)
+    assert layers > 0 and min(seen) >= HD.DLA_UP_MIN_OFFSET, seen
+    out32, g32 = HD.dla_up_run(ref, pyramid, cot, torch.float32)
+    names = sorted(g64)
+    gold = {
+        "keys": np.array(keys), "shapes": np.array([",".join(map(str, ref.state_dict()[k].shape)) for k in keys]),
+        "out": npy(out64), "out_fp32": npy(out32),
+        "grad_names": np.array(names),
+        "grad_norm": np.array([float(g64[k].norm()) for k in names]),
+        "grad_fp32_dev": np.array([float((g32[k].double() - g64[k]).norm()) for k in names]),
+        "offset_mean_abs": np.array(seen[:layers]),
+    }
+    path = os.path.join(GOLD, "dla_up.npz")
+    np.savez_compressed(path, **gold)
+    print("dla_up: %d DCN layers, mean |offset| %.2f .. %.2f px, out %s, fp32 deviation max %.2e, %d gradients, %d KiB" % (
+        layers, min(seen), max(seen), tuple(out64.shape), float((out32.double() - out64).abs().max()), len(names),
+        os.path.getsize(path) // 1024))
+
+
 if __name__ == "__main__":
+    if "--only-dla-up" in sys.argv:
+        gen_dla_up()
+        sys.exit(0)
     if "--only-motion-mask" in sys.argv:
         gen_motion_mask()
         sys.exit(0)
@@ -1719,5 +1772,6 @@ if __name__ == "__main__":
     gen_velo_gt()
     gen_postopt()
     gen_motion_mask()
+    gen_dla_up()
     for f in sorted(os.listdir(GOLD)):
         print(f, os.path.getsize(os.path.join(GOLD, f)) // 1024, "KiB")
