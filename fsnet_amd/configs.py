@@ -26,6 +26,8 @@ def meta_arch_cfg(height=192, width=640, with_pose=True, depth=18, num_output_ch
                                scales=list(scales), min_depth=min_depth, max_depth=max_depth))
     if base_fx is not None:
         head['depth_decoder_cfg']['base_fx'] = base_fx
+    if fisheye and len(frame_ids) != 3:
+        head['n_frame_kernels'] = True     # FishEyeDecoder: another count than two source frames (fs_photo_mei_multi_*)
     cfg = dict(depth_backbone_cfg=backbone, head_cfg=head, train_cfg=EasyDict(frame_ids=list(frame_ids)),
                test_cfg=EasyDict())
     if with_pose:

@@ -1,6 +1,6 @@
 // Body of the fused photometric backward, shared by photo_fused.hip (two source frames, pinhole and fisheye) and
-// photo_multi.hip (one to four source frames, pinhole): the kernels differ in how a wave finds its source frame and in
-// the argument struct, which the policy `FR` answers — everything else is this one text.  Included after
+// photo_multi.hip / photo_mei_multi.hip (one to four source frames, pinhole / fisheye): the kernels differ in how a
+// wave finds its source frame and in the argument struct, which the policy `FR` answers — everything else is this one text.  Included after
 // photo_common.h by files that allow fused multiply-adds (FS_PHOTO_CONTRACT_FAST).
 #pragma once
 #pragma clang fp contract(fast)

@@ -1,5 +1,5 @@
 // Device helpers shared by the photometric kernels (photometric.hip: setup, identity planes, pose gradient;
-// photo_fused.hip / photo_multi.hip: the fused forward and backward over two / one to four source frames):
+// photo_fused.hip / photo_multi.hip, photo_mei_multi.hip: the fused forward and backward over two / one to four source frames):
 // per-pixel geometry (depth upsample -> backproject -> project, pinhole and Mei fisheye), bilinear sampler taps,
 // tie-break noise, the frame-count policy, the launch helpers.  Reference call sites: monodepth2_decoder.py:61-116,355-411; monodepth_utils.py:101-165;
 // mei_fisheye_utils.py:14-51.
@@ -85,8 +85,10 @@ __device__ __forceinline__ void upsample_taps(int y, int x, int H, int W, int h,
 }
 
 // ray of pixel (y, x) and the depth (fisheye: ray norm) bilinearly upsampled from the scale's map -> g.D, g.r, taps
-__device__ __forceinline__ void pixel_ray(const FsPhotoArgs& p, const float* __restrict__ depth, int b, int y, int x,
-                                          int H, int W, int h, int w, const float* __restrict__ ge, Geo& g) {
+// (A: an argument struct with the ray-table fields, FsPhotoArgs or FsPhotoMeiMultiArgs)
+template <class A>
+__device__ __forceinline__ void pixel_ray(const A& p, const float* __restrict__ depth, int b, int y, int x, int H, int W,
+                                          int h, int w, const float* __restrict__ ge, Geo& g) {
   upsample_taps(y, x, H, W, h, w, g);
   const float* d = depth + (long)b * h * w;
   float d00 = d[g.y0 * w + g.x0], d01 = d[g.y0 * w + g.x1], d10 = d[g.y1 * w + g.x0], d11 = d[g.y1 * w + g.x1];
@@ -104,8 +106,9 @@ __device__ __forceinline__ void pixel_ray(const FsPhotoArgs& p, const float* __r
 }
 
 // the point D * r through frame f's transform / projection -> sample coordinates in the source frame
-__device__ __forceinline__ void project_ray(const FsPhotoArgs& p, int b, int H, int W, const float* __restrict__ ge,
-                                            int f, Geo& g) {
+template <class A>
+__device__ __forceinline__ void project_ray(const A& p, int b, int H, int W, const float* __restrict__ ge, int f,
+                                            Geo& g) {
   const float* P = ge + 18 + f * 12;
   if (p.lut_ptrs) {
     // FishEyeDecoder._generate_images_pred (monodepth2_decoder.py:355-387): point = ray table x norm, T, cam2image
@@ -131,9 +134,9 @@ __device__ __forceinline__ void project_ray(const FsPhotoArgs& p, int b, int H, 
   g.iyu = (vn + 1.f) * 0.5f * (float)(H - 1);
 }
 
-__device__ __forceinline__ void project_pixel(const FsPhotoArgs& p, const float* __restrict__ depth, int b, int y,
-                                              int x, int H, int W, int h, int w, const float* __restrict__ ge, int f,
-                                              Geo& g) {
+template <class A>
+__device__ __forceinline__ void project_pixel(const A& p, const float* __restrict__ depth, int b, int y, int x, int H,
+                                              int W, int h, int w, const float* __restrict__ ge, int f, Geo& g) {
   pixel_ray(p, depth, b, y, x, H, W, h, w, ge, g);
   project_ray(p, b, H, W, ge, f, g);
 }
@@ -171,7 +174,8 @@ __device__ __forceinline__ float tie_noise(int seed, uint32_t key) {
 
 // ---------------------------------------------------------------------------------------------
 // Frame-count policy: what the two-source kernels (FsPhotoArgs: frame_ids = [0, a, b], pinhole and fisheye) know at
-// compile time and the N-frame ones (FsPhotoMultiArgs: one to four sources, pinhole) read from the launch.  The kernel
+// compile time and the N-frame ones (FsPhotoMultiArgs: one to four sources, pinhole; FsPhotoMeiMultiArgs: the same counts
+// on the ray-table chain) read from the launch.  The kernel
 // bodies (photo_fwd_body.h, photo_bwd_body.h, the identity rows of photometric.hip) are one text over it.
 //   count(p)            source frames of the launch
 //   pairs(n)            frame pairs a forward / identity wave walks: the two frames of a pair ride in one f2
@@ -179,7 +183,7 @@ __device__ __forceinline__ float tie_noise(int seed, uint32_t key) {
 //   split(rest, n, f)   take the frame index off a backward wave's number
 //   geo_stride(n)       floats of a sample's geo record
 //   has_ov_mask(p), ov_mask(p, i)   the mask the overlap sample reads: patched_mask, or the fisheye chain's
-//                       patched_mask x ray-table mask (FsPhotoMultiArgs has no such plane)
+//                       patched_mask x ray-table mask (FsPhotoMultiArgs has no such plane, FsPhotoMeiMultiArgs has)
 // ---------------------------------------------------------------------------------------------
 struct TwoFrames {
   template <class A> static __device__ __forceinline__ int count(const A&) { return 2; }
@@ -201,6 +205,14 @@ struct NFrames {
   static __device__ __forceinline__ bool has_ov_mask(const FsPhotoMultiArgs& p) { return p.patched_mask != nullptr; }
   static __device__ __forceinline__ float ov_mask(const FsPhotoMultiArgs& p, long i) { return (float)p.patched_mask[i]; }
 };
+// NFrames on the ray-table chain: the frame walk of NFrames, the overlap plane of the two-source fisheye kernels
+struct NFramesMei : NFrames {
+  static __device__ __forceinline__ int count(const FsPhotoMeiMultiArgs& p) { return p.nsrc; }
+  static __device__ __forceinline__ bool has_ov_mask(const FsPhotoMeiMultiArgs& p) { return p.warp_mask || p.patched_mask; }
+  static __device__ __forceinline__ float ov_mask(const FsPhotoMeiMultiArgs& p, long i) {
+    return p.warp_mask ? p.warp_mask[i] : (float)p.patched_mask[i];
+  }
+};
 
 // ---------------------------------------------------------------------------------------------
 // host side of every strip launch
@@ -214,7 +226,7 @@ template <class Args> inline bool photo_args_ok(const Args* a, int nsrc) {
 }
 template <class Args> inline bool photo_planes_32bit(const Args* a) { return (long)a->H * a->W * 3 < 0x40000000L; }
 // the ray tables come with their parameters
-inline bool photo_fisheye_ok(const FsPhotoArgs* a) { return (a->lut_ptrs != nullptr) == (a->mei != nullptr); }
+template <class Args> inline bool photo_fisheye_ok(const Args* a) { return (a->lut_ptrs != nullptr) == (a->mei != nullptr); }
 // waves -> blocks of four (256 threads), rounded up to a multiple of `round` (8: whole XCD rounds, for the kernels that
 // re-order their blocks per XCD)
 inline long photo_blocks(long nwaves, int round) { return ((nwaves + 3) / 4 + round - 1) / round * round; }

@@ -1,5 +1,6 @@
 // Body of the fused photometric forward, shared by photo_fused.hip (two source frames, pinhole and fisheye) and
-// photo_multi.hip (one to four source frames, pinhole), as photo_bwd_body.h is for the backward: the kernels differ in
+// photo_multi.hip / photo_mei_multi.hip (one to four source frames, pinhole / fisheye), as photo_bwd_body.h is for the
+// backward: the kernels differ in
 // how many frame pairs a wave walks, where the running minimum waits between two walks and in the argument struct, which
 // the policy `FR` (photo_common.h) answers — everything else is this one text.  Included after photo_common.h and
 // photo_bwd_body.h (F2u, ldg2) by files that allow fused multiply-adds (FS_PHOTO_CONTRACT_FAST).
@@ -36,8 +37,8 @@ struct Row {       // one image row of a strip: horizontal 3-tap sums + the raw 
 };
 
 // FISH = false: pinhole geometry inlined with per-lane / per-row invariants hoisted and reciprocals by v_rcp_f32
-// (1 ulp; the staged kernels divide) — a sample coordinate moves by < 1e-4 px.  FISH = true (FsPhotoArgs only): the
-// shared ray-table geometry (photo_common.h).
+// (1 ulp; the staged kernels divide) — a sample coordinate moves by < 1e-4 px.  FISH = true (FsPhotoArgs,
+// FsPhotoMeiMultiArgs): the shared ray-table geometry (photo_common.h).
 // s_best / s_bi: the wave's slot [row][lane] of the running minimum (nullptr where FR walks one pair).
 template <bool WRITE_PRED, bool FISH, class FR, class Args>
 __device__ __forceinline__ void photo_fwd_body(const Args& p, int SX, int SY, int nwaves, float (*s_best)[64],
@@ -133,7 +134,7 @@ __device__ __forceinline__ void photo_fwd_body(const Args& p, int SX, int SY, in
       if constexpr (FISH) {
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
-          project_ray(p, b, H, W, ge, f, g);
+          project_ray(p, b, H, W, ge, f ? fb : fa, g);     // the pair's geo entries (TwoFrames: 0, 1)
           ixu2[f] = g.ixu; iyu2[f] = g.iyu;
         }
       } else {

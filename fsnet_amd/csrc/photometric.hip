@@ -361,9 +361,10 @@ extern "C" int fs_photo_setup(const float* P2, const float* T0, const float* T1,
   return fs_launch_status();
 }
 
-extern "C" int fs_photo_multi_setup(const float* P2, const float* const* T, int nsrc, float* geo, int B,
-                                    int* seed_counter, void* stream) {
-  if (!P2 || !T || !geo || nsrc < 1 || nsrc > MAXF || B < 1) return FS_EINVAL;
+// the N-frame setup launch; fisheye: P2 is not read (K = identity)
+static int launch_multi_setup(const float* P2, const float* const* T, int nsrc, float* geo, int B, int* seed_counter,
+                              int fisheye, void* stream) {
+  if (!T || !geo || nsrc < 1 || nsrc > MAXF || B < 1) return FS_EINVAL;
   PtrTable<const float> tp = {};
   for (int f = 0; f < nsrc; ++f) {
     if (!T[f]) return FS_EINVAL;
@@ -371,8 +372,19 @@ extern "C" int fs_photo_multi_setup(const float* P2, const float* const* T, int 
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(photo_setup_kernel, dim3((B + 63) / 64), dim3(64), 0, st, P2, tp, nsrc, geo_stride_n(nsrc), geo, B,
-                     seed_counter, 0);
+                     seed_counter, fisheye);
   return fs_launch_status();
+}
+
+extern "C" int fs_photo_multi_setup(const float* P2, const float* const* T, int nsrc, float* geo, int B,
+                                    int* seed_counter, void* stream) {
+  if (!P2) return FS_EINVAL;
+  return launch_multi_setup(P2, T, nsrc, geo, B, seed_counter, 0, stream);
+}
+
+extern "C" int fs_photo_mei_multi_setup(const float* const* T, int nsrc, float* geo, int B, int* seed_counter,
+                                        void* stream) {
+  return launch_multi_setup(nullptr, T, nsrc, geo, B, seed_counter, 1, stream);
 }
 
 extern "C" int fs_photo_identity(const FsPhotoArgs* a, void* stream) {

@@ -161,6 +161,13 @@ class FsPhotoMultiArgs(C.Structure):
     ]
 
 
+class FsPhotoMeiMultiArgs(C.Structure):
+    # FsPhotoMultiArgs field for field, then the ray-table fields (a pointer to it serves fs_photo_multi_identity too)
+    _fields_ = FsPhotoMultiArgs._fields_ + [
+        ("lut_ptrs", C.c_void_p), ("mei", C.c_void_p), ("warp_mask", C.c_void_p),
+    ]
+
+
 class FsSmoothArgs(C.Structure):
     _fields_ = [
         ("disp", C.c_void_p * 4), ("color", C.c_void_p * 4), ("d_disp", C.c_void_p * 4),

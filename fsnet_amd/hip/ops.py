@@ -7,7 +7,7 @@ import torch
 from torch.nn.modules.utils import _pair
 
 from .binding import (lib, check, stream_ptr, FsBnApplyArgs, FsBnBwdArgs, FsDcnArgs, FsDistillUnscaledArgs, FsFlowArgs,
-                      FsMotionMaskArgs, FsPhotoArgs, FsPhotoMultiArgs, FsPostOptArgs, FsSmoothArgs)
+                      FsMotionMaskArgs, FsPhotoArgs, FsPhotoMeiMultiArgs, FsPhotoMultiArgs, FsPostOptArgs, FsSmoothArgs)
 from .conv import dtype_code, roundup, _timed, BN_EPS, BN_MOMENTUM, Spec, run_specs
 
 STAT_SLOTS = 8   # FS_STAT_SLOTS in include/fsnet_hip.h
@@ -418,7 +418,7 @@ class _PhotoBackend:
         self.setup, self.identity, self.fwd, self.bwd, self.pose_grad, self.bwd_tiles = setup, identity, fwd, bwd, pose_grad, bwd_tiles
 
 
-def _photo_backend(multi):
+def _photo_backend(multi, fisheye=False):
     if not multi:        # frame_ids = [0, a, b], pinhole and fisheye: fs_photo_*
         return _PhotoBackend(
             "photo_fused", FsPhotoArgs, lambda n: 48,
@@ -434,19 +434,33 @@ def _photo_backend(multi):
             pl._Tp[f] = Ts[f].data_ptr() if f < pl.nsrc else None
         return lib.fs_photo_multi_setup(P2.data_ptr(), pl._Tp, pl.nsrc, pl.geo.data_ptr(), pl.B, seed, st)
 
+    def pose_grad(pl, st):
+        return lib.fs_photo_multi_pose_grad(pl.geo.data_ptr(), pl.dP.data_ptr(), pl._dT.data_ptr(), pl.nsrc, pl.B, pl.S,
+                                            pl.bwd_tiles, st)
+
+    if fisheye:
+        def setup_mei(pl, P2, Ts, seed, st):
+            for f in range(4):
+                pl._Tp[f] = Ts[f].data_ptr() if f < pl.nsrc else None
+            return lib.fs_photo_mei_multi_setup(pl._Tp, pl.nsrc, pl.geo.data_ptr(), pl.B, seed, st)
+
+        return _PhotoBackend(  # one to four sources on the Mei ray tables: fs_photo_mei_multi_* (identity planes, tiles and
+            #                    pose gradient have no geometry of their own: the pinhole chain's)
+            "photo_mei_multi", FsPhotoMeiMultiArgs, lambda n: 18 + 12 * n, setup_mei,
+            lib.fs_photo_multi_identity, lib.fs_photo_mei_multi_fwd, lib.fs_photo_mei_multi_bwd, pose_grad,
+            lib.fs_photo_multi_bwd_tiles)
     return _PhotoBackend(      # one to four sources, pinhole: fs_photo_multi_*
         "photo_multi", FsPhotoMultiArgs, lambda n: 18 + 12 * n, setup,
-        lib.fs_photo_multi_identity, lib.fs_photo_multi_fwd, lib.fs_photo_multi_bwd,
-        lambda pl, st: lib.fs_photo_multi_pose_grad(pl.geo.data_ptr(), pl.dP.data_ptr(), pl._dT.data_ptr(), pl.nsrc, pl.B,
-                                                    pl.S, pl.bwd_tiles, st),
+        lib.fs_photo_multi_identity, lib.fs_photo_multi_fwd, lib.fs_photo_multi_bwd, pose_grad,
         lib.fs_photo_multi_bwd_tiles)
 
 
 class PhotometricLoss:
     """Fused loss chain for one batch geometry (B, H, W, scales) over nsrc = 1..4 source frames.  forward() returns the
     loss vector (f64 [2S+1]: loss/s, smooth_loss/s, total); backward() returns d depth_s and dT_f (nsrc [B,4,4] views).
-    nsrc == 2 runs the two-source kernels (fs_photo_*; the only ones with the fisheye model), every other count the
-    N-frame ones (fs_photo_multi_*); force_multi=True puts nsrc == 2 on those as well (their tests).
+    nsrc == 2 runs the two-source kernels (fs_photo_*), every other count the N-frame ones (fs_photo_multi_*; after
+    stage_fisheye() their ray-table form fs_photo_mei_multi_*); force_multi=True puts nsrc == 2 on those as well (their
+    tests).
     want_pred: also materialise the warped images / overlap masks (self.pred, self.ov) — only needed for logging and
     for the ("original_image", f, s) entries the reference leaves in its output dict."""
 
@@ -522,9 +536,12 @@ class PhotometricLoss:
     def stage_fisheye(self, tables, mei_rows):
         """tables: B device tensors [4,H,W] (fs_mei_lut); mei_rows: host float32 [B,8] = k1 k2 xi g1 g2 u0 v0 0.
         Copies the pointer table and the parameters into persistent device buffers on the current stream."""
-        if self.multi:
-            raise NotImplementedError("the fisheye loss chain runs two source frames (ops.PhotometricLoss)")
         B, dev = self.B, self.device
+        if self.multi and self._be.args is not FsPhotoMeiMultiArgs:
+            # the N-frame engine moves to the ray-table entry points: same buffers and layouts, the argument struct grows
+            # by the three ray-table fields
+            self._be = _photo_backend(True, fisheye=True)
+            self._pa = self._be.args()
         if self.lut_table is None:
             self.lut_table = torch.zeros(B, dtype=torch.int64, device=dev)
             self.mei = torch.zeros(B, 8, dtype=torch.float32, device=dev)
@@ -591,11 +608,10 @@ class PhotometricLoss:
         pa.gout = _p(gout)
         pa.noise_seed = -1 if noise_seed is None else int(noise_seed)
         pa.noise_seed_ptr = self.seed_buf.data_ptr() if noise_seed is None else None
-        if not self.multi:
-            if self.fisheye:
-                pa.lut_ptrs, pa.mei, pa.warp_mask = self.lut_table.data_ptr(), self.mei.data_ptr(), self.warp_mask.data_ptr()
-            else:
-                pa.lut_ptrs = pa.mei = pa.warp_mask = None
+        if self.fisheye:
+            pa.lut_ptrs, pa.mei, pa.warp_mask = self.lut_table.data_ptr(), self.mei.data_ptr(), self.warp_mask.data_ptr()
+        elif not self.multi:
+            pa.lut_ptrs = pa.mei = pa.warp_mask = None
         pa.motion_mask = _p(self.motion_mask)
         sa.disp_sum, sa.sm_sums, sa.dot = self.disp_sum.data_ptr(), self.sm_sums.data_ptr(), self.dot.data_ptr()
         sa.gout = _p(gout)

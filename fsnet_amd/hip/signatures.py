@@ -111,6 +111,10 @@ SIGNATURES = {
     "fs_photo_multi_bwd_tiles": (C.c_int64, [I, I]),
     "fs_photo_multi_pose_grad": (C.c_int, [P, P, P, I, I, I, I, P]),
     "fs_photo_multi_strip": (C.c_int, [I, P, P]),
+    # added under ABI 15: the same chain on the fisheye ray tables (FsPhotoMeiMultiArgs)
+    "fs_photo_mei_multi_setup": (C.c_int, [P, I, P, I, P, P]),
+    "fs_photo_mei_multi_fwd": (C.c_int, [P, P]),
+    "fs_photo_mei_multi_bwd": (C.c_int, [P, P]),
     "fs_augment_frames": (C.c_int, [P, P]),
     "fs_resize_frames": (C.c_int, [P, P]),
     "fs_augment_frames_masked": (C.c_int, [P, P, P]),

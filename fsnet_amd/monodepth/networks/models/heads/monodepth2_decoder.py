@@ -298,7 +298,8 @@ class FishEyeDecoder(MonoDepth2Decoder):
     """MonoDepth2Decoder for the Mei unified fisheye model (monodepth2_decoder.py:350-420): the network output is the
     ray norm, the 3-D point is the per-calibration ray table x norm, the relative pose acts on it directly and
     cam2image (mirror + radial distortion) maps it into the source frame; the overlap mask samples
-    patched_mask x table mask.  Same fused HIP loss chain, ray-table variant (FsPhotoArgs.lut_ptrs)."""
+    patched_mask x table mask.  Same fused HIP loss chain, ray-table variant (FsPhotoArgs.lut_ptrs; one, three or four
+    source frames: FsPhotoMeiMultiArgs)."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -307,11 +308,18 @@ class FishEyeDecoder(MonoDepth2Decoder):
         self._staged = None          # (P2 tensor, its version, calib list) of the last staging: strong references,
         self._hook_staged = False    # so an equal identity really is the same batch object
 
+    # head option (not in the reference): frame_ids of another length than [0, a, b] run the ray-table N-frame kernels
+    # (fs_photo_mei_multi_*).  Without it such a list is refused as it always was: that refusal is pinned behaviour
+    # (tests/test_photo64n_cpu.py, tests/test_distill_unscaled_cpu.py).  configs.meta_arch_cfg(fisheye=True) sets it
+    # whenever the list it is given needs it.
+    n_frame_kernels = False
+
     def _check_frame_ids(self):
         super()._check_frame_ids()
-        if len(self.frame_ids) != 3:
-            raise NotImplementedError("FishEyeDecoder: frame_ids %r — the ray-table (Mei) loss kernels run exactly two "
-                                      "source frames, [0, a, b]" % (self.frame_ids,))
+        if len(self.frame_ids) != 3 and not getattr(self, "n_frame_kernels", False):
+            raise NotImplementedError("FishEyeDecoder: frame_ids %r — the two-source ray-table (Mei) loss kernels run "
+                                      "exactly two source frames, [0, a, b]; set the head option n_frame_kernels=True "
+                                      "for the N-frame ones" % (self.frame_ids,))
 
     def stage_step_inputs(self, input_dict, from_hook=True):
         """ray tables of this batch's calibrations (built once each, cached by the reference's key) -> the loss

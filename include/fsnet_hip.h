@@ -865,6 +865,46 @@ int fs_photo_multi_pose_grad(const float* geo, const float* dP, float* dT, int n
 /* output columns and rows of one wave's strip: which = 0 identity, 1 forward, 2 backward */
 int fs_photo_multi_strip(int which, int32_t* cols, int32_t* rows);
 
+/* The N-frame chain on the fisheye / Mei ray tables (photo_mei_multi.hip; FishEyeDecoder with frame_ids = [0, a, ...],
+ * nsrc = 1..4; added under ABI 15, everything above is untouched).  Per frame the arithmetic is that of fs_photo_fused_* with lut_ptrs set; the
+ * layouts (geo, ident, pred, ov, dP, sel) are those of fs_photo_multi_*.  FsPhotoMeiMultiArgs is FsPhotoMultiArgs field
+ * for field, followed by the three ray-table fields of FsPhotoArgs: a pointer to it is what fs_photo_multi_identity
+ * takes as well (the identity planes have no geometry), and fs_photo_multi_bwd_tiles / _strip / _pose_grad serve this
+ * chain as they are (K = identity: the pose gradient is dT itself).  fs_photo_mei_multi_fwd / _bwd return FS_EINVAL
+ * without touching the device for what fs_photo_multi_* refuse and for lut_ptrs or mei missing; warp_mask may be NULL
+ * (the overlap sample then reads patched_mask alone, as in fs_photo_fused_fwd). */
+typedef struct FsPhotoMeiMultiArgs {
+  const float* img0;
+  const float* img_src[4];      /* the first nsrc are read */
+  const double* patched_mask;   /* [B][H][W] or NULL (= ones) */
+  const float* depth[4];        /* per scale [B][dh][dw]: the ray norm */
+  const float* geo;
+  float* pred;
+  uint8_t* ov;
+  float* ident;
+  uint8_t* sel;
+  double* loss_sums;            /* [S][B] */
+  double* mask_sum;             /* [B] */
+  float* d_depth[4];
+  float* dP;
+  const double* gout;
+  int32_t dh[4], dw[4];
+  int32_t B, H, W, S;
+  int32_t nsrc;
+  int32_t noise_seed;
+  const int32_t* noise_seed_ptr;
+  const float* motion_mask;
+  int32_t no_overlap_mask;
+  int32_t reserved0;
+  const float* const* lut_ptrs;   /* as FsPhotoArgs: device array [B] of ray tables [4][H][W] */
+  const float* mei;               /* device [B][8] */
+  const float* warp_mask;         /* [B][H][W] fp32 = patched_mask x ray-table mask (fs_mei_stage_mask) or NULL */
+} FsPhotoMeiMultiArgs;
+/* geo [B][18 + 12 nsrc] with K = K^-1 = identity and P_f = T_f[:3]; T and seed_counter as in fs_photo_multi_setup */
+int fs_photo_mei_multi_setup(const float* const* T, int nsrc, float* geo, int B, int* seed_counter, void* stream);
+int fs_photo_mei_multi_fwd(const FsPhotoMeiMultiArgs* args, void* stream);
+int fs_photo_mei_multi_bwd(const FsPhotoMeiMultiArgs* args, void* stream);
+
 /* Mei unified fisheye camera model (mei_fisheye_utils.py:14-187; configs/kitti360_fisheye_example:198-207).
  * fs_mei_lut: the per-calibration table MeiCameraProjection.image2cam caches (:150-166) — for every pixel the radial
  *   distortion is inverted by Newton (newton_methods :70-79) and the mirror equation by bisection (bisection_methods

@@ -768,6 +768,70 @@ def gen_fisheye():
     np.savez_compressed(os.path.join(GOLD, "fisheye.npz"), **out)
 
 
+def gen_fisheye_nsrc():
+    """gen_fisheye's loss chain for frame_ids of other lengths: the REAL FishEyeDecoder.loss with 1, 3 and 4 temporal
+    source frames at 64 x 64, B = 2, on the inputs of tests/helpers_fisheye_n.py (every candidate of the per-pixel minimum
+    wins somewhere) -> inputs, per-scale losses, total, gradients, the scale-0 warp (thinned ::2) and overlap masks, and
+    min_idx from the oracle under the same noise (fisheye_nsrc.npz)."""
+    from oracle import fisheye_oracle as FO
+    from tests import helpers_fisheye_n as Q
+    out = {}
+    for N in (1, 3, 4):
+        case = Q.make_case("golden-n%d" % N)
+        fids, H, W, data = list(case["fids"]), case["H"], case["W"], case["data"]
+        tag = "n%d_" % N
+        dec = build(name='monodepth.networks.models.heads.monodepth2_decoder.FishEyeDecoder', scales=[0, 1, 2, 3],
+                    height=H, width=W, frame_ids=fids, min_depth=0.5, max_depth=150.0, overlapped_mask=True,
+                    is_log_image=False,
+                    depth_decoder_cfg=dict(name='monodepth.networks.models.heads.depth_encoder.MultiChannelDepthDecoder',
+                                           num_ch_enc=np.array([64, 64, 128, 256, 512]), num_output_channels=64,
+                                           use_skips=True, scales=[0, 1, 2, 3], min_depth=0.5, max_depth=150))
+        outputs, leaves = {}, {}
+        for s in range(4):
+            d = case["depths"][s].clone().requires_grad_(True)
+            leaves[("depth", s)] = d
+            outputs[("depth", s, s)] = d
+            outputs[("disp", s)] = mu.depth_to_disp(d, 0.5, 150.0)
+        for f in fids[1:]:
+            aa, tr = case["aa"][f].clone().requires_grad_(True), case["tr"][f].clone().requires_grad_(True)
+            leaves[("aa", f)], leaves[("tr", f)] = aa, tr
+            outputs[("cam_T_cam", f)] = mu.transformation_from_parameters(aa, tr, invert=(f < 0))
+        torch.manual_seed(0)
+        res = dec.loss(outputs, data)
+        res['loss'].backward()
+        out[tag + "frame_ids"] = np.asarray(fids, np.int64)
+        out[tag + "seed"] = np.int64(case["seed"])
+        out[tag + "total_loss"] = npy(res['loss'])
+        for k, v in res['loss_dict'].items():
+            out[tag + "ld_" + k.replace('/', '_')] = npy(v)
+        for s in range(4):
+            out[tag + "depth_%d" % s] = npy(leaves[("depth", s)])
+            out[tag + "gdepth_%d" % s] = npy(leaves[("depth", s)].grad)
+        for f in fids[1:]:
+            out[tag + "aa_%d" % f], out[tag + "tr_%d" % f] = npy(leaves[("aa", f)]), npy(leaves[("tr", f)])
+            out[tag + "gaa_%d" % f], out[tag + "gtr_%d" % f] = npy(leaves[("aa", f)].grad), npy(leaves[("tr", f)].grad)
+            out[tag + "warp0_%d" % f] = npy(outputs[("original_image", f, 0)])[:, :, ::2, ::2]
+            out[tag + "ovmask0_%d" % f] = npy(outputs[("overlapped_mask", f, 0)])
+        for f in fids:
+            out[tag + "img8_%d" % f] = case["u8"][f]         # the frame is uint8 / 255 (helpers_fisheye_n.image_from_u8)
+        out[tag + "P2"] = npy(data["P2"]); out[tag + "patched_mask"] = npy(data["patched_mask"]).astype(np.uint8)
+        # cross-check the oracle under the same tie-break noise, and take min_idx from it (the reference keeps its index
+        # in a local variable)
+        o = Q.oracle_chain(case, noise=Q.reference_noise(case), grads=True)
+        for s in range(4):
+            out[tag + "minidx_%d" % s] = npy(o["outputs"][("min_idx", s)]).astype(np.uint8)
+        f1 = fids[1]
+        print("fisheye chain N=%d: ref loss %.9f oracle %.9f | gdepth0 dev rel %.3e | warp dev %.3e | ov mismatches %d" % (
+            N, float(res['loss']), float(o["total"]),
+            dev(o["depths"][0].grad, leaves[("depth", 0)].grad) / float(leaves[("depth", 0)].grad.abs().max()),
+            dev(o["outputs"][("original_image", f1, 0)], outputs[("original_image", f1, 0)]),
+            int((o["outputs"][("overlapped_mask", f1, 0)] != outputs[("overlapped_mask", f1, 0)]).sum())))
+    out["calib"] = np.array([[c["distortion_parameters"]["k1"], c["distortion_parameters"]["k2"],
+                              c["mirror_parameters"]["xi"]] for c in data["calib_meta"]])
+    out.update(H=H, W=W)
+    np.savez_compressed(os.path.join(GOLD, "fisheye_nsrc.npz"), **out)
+
+
 def gen_model_r50fx():
     """BASELINE configs[4] wiring at a small size: MonoDepthWPose, ResNet-50 (Bottleneck), 64 depth bins,
     base_fx = 492 (configs/multi_dataset_example:227-257) with per-sample focal lengths; forward tensors, loss_dict and
@@ -1681,6 +1745,9 @@ if __name__ == "__main__":
     if "--only-nsrc" in sys.argv:
         gen_loss_chain_nsrc()
         sys.exit(0)
+    if "--only-fisheye-nsrc" in sys.argv:
+        gen_fisheye_nsrc()
+        sys.exit(0)
     if "--only-postopt" in sys.argv:
         gen_postopt()
         sys.exit(0)
@@ -1754,6 +1821,7 @@ if __name__ == "__main__":
     gen_distill_unscaled()
     gen_augment()
     gen_fisheye()
+    gen_fisheye_nsrc()
     gen_model_r50fx()
     gen_kitti_dataset()
     gen_kitti_eigen_test_dataset()
