@@ -80,6 +80,17 @@ class FsAugArgs(C.Structure):
     ]
 
 
+class FsAugExtArgs(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("minv", C.c_void_p), ("dims", C.c_void_p), ("win", C.c_void_p), ("ops", C.c_void_p),
+        ("opv", C.c_void_p), ("mask_src", C.c_void_p),
+        ("image", C.c_void_p), ("original", C.c_void_p), ("mask", C.c_void_p),
+        ("mean", C.c_float * 3), ("std", C.c_float * 3),
+        ("B", C.c_int32), ("F", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("n_ops", C.c_int32), ("split", C.c_int32),
+    ]
+
+
 class FsHeadBatch(C.Structure):
     _fields_ = [
         ("logits", C.c_void_p * 4), ("depth", C.c_void_p * 4), ("disp", C.c_void_p * 4),

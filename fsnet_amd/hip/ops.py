@@ -1237,6 +1237,18 @@ def augment_masks(src, H, W, minv=None, dims=None, iplan=None):
     return out
 
 
+def augment_masks_ext(src, H, W, dims, win, minv=None):
+    """the same masks through the windowed plan of fs_augment_frames_ext (minv [B,6] f64) or fs_resize_frames_ext
+    (minv None): dims [B,4] int32, win [B,8] int32 -> fp32 [B,H,W]"""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.dim() == 3
+    B, Hs, Ws = src.shape
+    src = src.contiguous()
+    out = torch.empty(B, H, W, dtype=torch.float32, device=src.device)
+    check(lib.fs_augment_masks_ext(src.data_ptr(), _p(minv), _p(dims), _p(win), out.data_ptr(), B, Hs, Ws, H, W,
+                                   stream_ptr()), "augment_masks_ext")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # self-distillation (SURVEY 8f rank 3)
 # ---------------------------------------------------------------------------------------------

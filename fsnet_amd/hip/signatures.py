@@ -119,6 +119,10 @@ SIGNATURES = {
     "fs_resize_frames": (C.c_int, [P, P]),
     "fs_augment_frames_masked": (C.c_int, [P, P, P]),
     "fs_resize_frames_masked": (C.c_int, [P, P, P]),
+    # added under ABI 15: the same launches with an output window and a colour op list (FsAugExtArgs)
+    "fs_augment_frames_ext": (C.c_int, [P, P]),
+    "fs_resize_frames_ext": (C.c_int, [P, P]),
+    "fs_augment_masks_ext": (C.c_int, [P, P, P, P, P, I, I, I, I, I, P]),
     "fs_color_pyramid": (C.c_int, [P, P, I, I, I, I, I, P]),
     # added under ABI 15: (img, outs[n], hs[n], ws[n], n, B, H, W, stream) — all levels from one read of the image
     "fs_color_pyramid_multi": (C.c_int, [P, P, P, P, I, I, I, I, P]),

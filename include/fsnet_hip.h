@@ -380,6 +380,56 @@ int fs_resize_frames(const FsResizeArgs* args, void* stream);
 int fs_augment_frames_masked(const FsAugArgs* args, const uint8_t* mask_src, void* stream);
 int fs_resize_frames_masked(const FsResizeArgs* args, const uint8_t* mask_src, void* stream);
 
+/* The two launches with an output window and a colour op list (added under ABI 15; the entry points above are
+ * untouched and still serve every plan they can express).  They carry the rest of the reference's
+ * vision_base/data/augmentations/augmentations.py: CropTop :228-265, CropRight :268-301, Pad2Shape :304-324 and
+ * RandomCropToWidth :343-375 after the resampling stage, any number of RandomMirror :377-433 among them, RandomHue
+ * :500-524, RandomEigenvalueNoise :594-626, PhotometricDistort :628-666, Copy :668-680
+ * (configs/kitti360_fisheye_example:133-159 is the shipped chain with a Copy).
+ *   win[b]  = { flip, x_off, y_off, vx0, vy0, vx1, vy1, 0 }: output pixel (xo, yo) of the H x W result is canvas pixel
+ *             (flip ? x_off - xo : x_off + xo, y_off + yo) of the warp's / resize's own output when vx0 <= xo < vx1 and
+ *             vy0 <= yo < vy1, and np.pad's zero (image, mask) elsewhere; the zero passes the colour ops and Normalize.
+ *             An empty rectangle is legal: all padding.
+ *   ops[b]  = n_ops slots, kind | flags << 4: FS_AUGX_BRIGHTNESS (opv delta), FS_AUGX_CONTRAST (opv alpha),
+ *             FS_AUGX_HSV (RGB -> HSV -> RGB; flag 1: s *= opv[0], flag 2: h += opv[1], h > 360 -> h - 360, h < 0 ->
+ *             h + 360), FS_AUGX_NOISE (opv[0..2] added per channel), FS_AUGX_NOP.
+ *   opv[b]  = [FS_AUGX_OPS][3] f64.  fp32 arithmetic with the value rounded to fp32, as numpy does for a Python float
+ *             against a float32 image; from a noise slot on the pixel is f64 (numpy promotes float32 + float64) and is
+ *             rounded to fp32 once, by Normalize's astype.  An HSV slot after a noise slot does nothing.
+ *   split   = Copy: `original` is the pixel after the first `split` slots (0: the unaugmented frame), / 255.
+ * dims[b] = { src_h, src_w, rh, rw } (rh, rw: fs_resize_frames_ext only); minv: fs_augment_frames_ext only, NULL for
+ * the resize.  mask_src NULL: the mask of ones is synthesised.  Source and mask indices stay inside the Hs x Ws plane
+ * whatever the rows say.  FS_EINVAL: NULL src / dims / win, neither image nor original, minv on the wrong launch,
+ * mask_src without mask, a non-positive size, n_ops > FS_AUGX_OPS, split > n_ops, n_ops > 0 without ops / opv, std 0. */
+#define FS_AUGX_OPS 8
+#define FS_AUGX_WIN 8
+#define FS_AUGX_BRIGHTNESS 0
+#define FS_AUGX_CONTRAST 1
+#define FS_AUGX_HSV 2
+#define FS_AUGX_NOISE 3
+#define FS_AUGX_NOP 4
+typedef struct FsAugExtArgs {
+  const uint8_t* src;
+  const double* minv;
+  const int32_t* dims;
+  const int32_t* win;
+  const int32_t* ops;
+  const double* opv;
+  const uint8_t* mask_src;
+  float* image;
+  float* original;
+  double* mask;
+  float mean[3];
+  float std[3];
+  int32_t B, F, Hs, Ws, H, W, n_ops, split;
+} FsAugExtArgs;
+int fs_augment_frames_ext(const FsAugExtArgs* args, void* stream);
+int fs_resize_frames_ext(const FsAugExtArgs* args, void* stream);
+/* fs_augment_masks through the same window: src [B][Hs][Ws] uint8 -> out [B][H][W] fp32, INTER_NEAREST of the warp
+ * (minv) or the resize (minv NULL), 0 outside the valid rectangle. */
+int fs_augment_masks_ext(const uint8_t* src, const double* minv, const int32_t* dims, const int32_t* win, float* out,
+                         int B, int Hs, int Ws, int H, int W, void* stream);
+
 /* Evaluation.  fs_resize_linear: single-channel fp32 [h][w] -> [H][W] with OpenCV's INTER_LINEAR
  * rule; invert != 0 resizes the inverse: dst = 1 / resize(1 / src)  (base_evaluation_hooks.py:57).
  * fs_depth_eval: per image b, pred [B][h][w] (resized on the fly to the ground truth's [H][W]) against gt [B][H][W]:

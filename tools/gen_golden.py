@@ -670,6 +670,90 @@ def gen_augment_mask():
     np.savez_compressed(os.path.join(GOLD, "augment_mask.npz"), **res)
 
 
+def gen_augment_ext():
+    """The remaining augmentation classes (CropTop, Pad2Shape, RandomCropToWidth, RandomHue, RandomEigenvalueNoise,
+    PhotometricDistort, Copy; augmentations.py:228-375, :500-524, :594-680) through the REAL reference classes, built by
+    the reference's own builder over the six chains of tests/helpers_augment_ext.py.  cv2 is the shim's restatement
+    (unpinned, as in gen_augment).  The global seed of a case is the first one under which every RandomMirror of the
+    chain is drawn on and off among the four samples (and, case d, both contrast positions occur)."""
+    from tests import helpers_augment_ext as HX
+    if not hasattr(np, "int"):
+        np.int = int
+    ref_aug, ref_builder = 'vision_base.data.augmentations.augmentations', 'vision_base.utils.builder'
+    res = dict(frame_idxs=np.array(HX.FRAME_IDXS), sizes=np.array(HX.SIZES), mean=HX.MEAN, std=HX.STD)
+    maxdev = 0.0
+
+    def run(tag, c, global_seed, frame_seed):
+        np.random.seed(c["build_seed"])
+        ref = build(**HX.cfg(c["steps"], c["common"], ref_aug, ref_builder))
+        np.random.seed(c["build_seed"])
+        mine = HX.NumpyChain(c["steps"], c["common"])
+        np.random.seed(global_seed)
+        state = np.random.get_state()
+        outs, wants, logs = [], [], []
+        for n in range(len(HX.SIZES)):
+            np.random.set_state(state)
+            outs.append(ref(HX.sample(tag, n, frame_seed)))
+            after = np.random.get_state()
+            np.random.set_state(state)
+            wants.append(mine(HX.sample(tag, n, frame_seed)))
+            logs.append(mine.log)
+            mine_next = np.random.rand()
+            np.random.set_state(after)
+            assert mine_next == np.random.rand(), "the two chains consumed the global stream differently"
+            state = after
+        np.random.set_state(state)
+        return outs, wants, logs, np.random.rand()
+
+    for k, tag in enumerate(HX.CASES):
+        c = HX.case(tag)
+        frame_seed = 2000 + 10 * k
+        for global_seed in range(500 + 100 * k, 600 + 100 * k):
+            outs, wants, logs, nxt = run(tag, c, global_seed, frame_seed)
+            mirrors = np.array([l["mirrors"] for l in logs])
+            ok = bool(np.all(mirrors.any(0) & ~mirrors.all(0)))
+            if tag == "d":
+                ok = ok and len({l["contrast_first"] for l in logs}) == 2
+            if ok:
+                break
+        assert ok, tag
+        if tag == "e":
+            assert set().union(*[l["wraps"] for l in logs]) == {"up", "down"}, "the hue must wrap both ways"
+        res["%s_global_seed" % tag], res["%s_frame_seed" % tag], res["%s_next" % tag] = global_seed, frame_seed, nxt
+        res["%s_mirrors" % tag] = mirrors
+        for n, (out, want) in enumerate(zip(outs, wants)):
+            pre = "%s%d_" % (tag, n)
+            frames = range(1) if tag == "f" else range(len(HX.FRAME_IDXS))      # f pins the masks; c has its pixels
+            for j in frames:
+                i = HX.FRAME_IDXS[j]
+                for fam, short in (("image", "image"), ("original_image", "orig")):
+                    got = HX.chw(npy(out[(fam, i)]) if isinstance(out[(fam, i)], torch.Tensor) else out[(fam, i)])
+                    assert got.dtype == np.float32 and got.shape == (3,) + c["out_hw"], (tag, fam, got.dtype, got.shape)
+                    res[pre + "%s_%d" % (short, j)] = got
+                    maxdev = max(maxdev, float(np.abs(got - HX.chw(want[(fam, i)])).max()))
+            mask = npy(out['patched_mask'])
+            assert mask.dtype == np.float64 and set(np.unique(mask)) <= {0.0, 1.0}
+            res[pre + "mask"] = mask.astype(np.uint8)
+            maxdev = max(maxdev, float(np.abs(mask - want['patched_mask']).max()))
+            if tag == "f":
+                res[pre + "motion_mask"] = npy(out['motion_mask'])
+                maxdev = max(maxdev, float(np.abs(res[pre + "motion_mask"].astype(np.float64) - want['motion_mask']).max()))
+            res[pre + "P2"] = npy(out['P2'])
+            maxdev = max(maxdev, float(np.abs(res[pre + "P2"] - np.asarray(want['P2'], dtype=np.float32)).max()))
+            for j, i in enumerate(HX.FRAME_IDXS[1:]):
+                res[pre + "pose_%d" % j] = np.asarray(out[('relative_pose', i)])
+                maxdev = max(maxdev, float(np.abs(res[pre + "pose_%d" % j] - want[('relative_pose', i)]).max()))
+            for key in (('image_resize', 'original_shape'), ('image_resize', 'effective_size')):
+                if key in out:
+                    res[pre + key[1]] = np.asarray(out[key])
+        print("augment-ext case %s: global seed %d, mirrors %s%s" % (
+            tag, global_seed, mirrors.astype(int).tolist(),
+            ", contrast first %s" % [l["contrast_first"] for l in logs] if tag == "d" else ""))
+    print("augment-ext: numpy composition vs reference classes, max abs deviation %.3e" % maxdev)
+    np.savez_compressed(os.path.join(GOLD, "augment_ext.npz"), **res)
+    print("augment_ext.npz: %d bytes" % os.path.getsize(os.path.join(GOLD, "augment_ext.npz")))
+
+
 def gen_fisheye():
     """Fisheye path (BASELINE configs[3]) through the REAL classes: MeiCameraProjection LUT + cam2image
     (mei_fisheye_utils.py:14-187) and FishEyeDecoder.loss with gradients (monodepth2_decoder.py:350-420)."""
@@ -1784,6 +1868,9 @@ if __name__ == "__main__":
     if "--only-augment-mask" in sys.argv:
         gen_augment_mask()
         sys.exit(0)
+    if "--only-augment-ext" in sys.argv:
+        gen_augment_ext()
+        sys.exit(0)
     if "--only-fisheye" in sys.argv:
         gen_fisheye()
         sys.exit(0)
@@ -1841,5 +1928,6 @@ if __name__ == "__main__":
     gen_postopt()
     gen_motion_mask()
     gen_dla_up()
+    gen_augment_ext()
     for f in sorted(os.listdir(GOLD)):
         print(f, os.path.getsize(os.path.join(GOLD, f)) // 1024, "KiB")
