@@ -1,6 +1,6 @@
 // Nearest-neighbour source coordinates of the training input pipeline, in one place: the patched mask that rides in the
-// frames' launches (augment.hip) and the other ground-truth images (fs_augment_masks, optflow.hip) sample with the same
-// arithmetic as cv2.warpAffine / cv2.resize with INTER_NEAREST (oracle/augment_oracle.py warp_affine_nearest,
+// frames' launches and the other ground-truth images (fs_augment_masks), both through augment.hip's Sampler, sample with
+// the same arithmetic as cv2.warpAffine / cv2.resize with INTER_NEAREST (oracle/augment_oracle.py warp_affine_nearest,
 // resize_nearest; reference augmentations.py:163-164, :484-487).
 #pragma once
 #include <cstdint>

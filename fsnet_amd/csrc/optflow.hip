@@ -1,5 +1,6 @@
-// Dense optical flow and epipolar motion masks on the device, and the masks' way through the training input
-// pipeline.  The precompute half of the reference's motion-mask option:
+// Dense optical flow and epipolar motion masks on the device (the masks then travel through the training input
+// pipeline as ground-truth images: masks_kernel, augment.hip).  The precompute half of the reference's motion-mask
+// option:
 //   MotionMaskPrecomputeHook / MotionMaskARFlowPrecomputeHook (monodepth/pipeline_hooks/precomputing_hooks/
 //   base_precompute_hooks.py:27-148): cv2.cvtColor(BGR2GRAY) + cv2.calcOpticalFlowFarneback, then the per-pixel
 //   distance to the epipolar line of F = K^-T [T]x R K^-1 against a threshold.
@@ -18,7 +19,6 @@
 // No atomics, every sum in a fixed order: the result is bit-identical from run to run and across batchings.
 #include "common.h"
 #include "fsnet_hip_internal.h"
-#include "nearest.h"
 #include <cmath>
 
 namespace {
@@ -304,33 +304,6 @@ __global__ __launch_bounds__(256) void of_motion_mask(const FsMotionMaskArgs a) 
   a.mask[(long)b * HW + i] = q > a.threshold ? 1 : 0;
 }
 
-// -- ground-truth masks through the augmentation plan ---------------------------------------------------------------
-// uint8 [B][Hs][Ws] -> fp32 [B][H][W].  Warp (minv): cv2.warpAffine INTER_NEAREST coordinates of the patched_mask
-// branch of augment.hip, BORDER_CONSTANT 0.  Resize (dims): cv2.resize INTER_NEAREST, floor(d * scale) clamped,
-// zero padding / crop.  Then RandomMirror (iplan[4]).
-__global__ __launch_bounds__(256) void of_augment_masks(const uint8_t* src, const double* minv, const int32_t* dims,
-                                                         const int32_t* iplan, float* out, int Hs, int Ws, int H,
-                                                         int W) {
-  const int b = blockIdx.y;
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long)H * W) return;
-  const int y = (int)(i / W), xo = (int)(i - (long)y * W);
-  const int x = (iplan && iplan[b * FS_AUG_IPLAN + 4]) ? W - 1 - xo : xo;
-  const uint8_t* s = src + (long)b * Hs * Ws;
-  float v = 0.f;
-  if (minv) {
-    const int sh = iplan[b * FS_AUG_IPLAN + 5], sw = iplan[b * FS_AUG_IPLAN + 6];
-    long sx, sy;
-    if (fs_warp_nearest(fs_warp_fixed(minv + b * 6, x, y), sh, sw, sx, sy)) v = (float)s[sy * Ws + sx];
-  } else {
-    const int32_t* d = dims + b * 4;
-    const int sh = d[0], sw = d[1], rh = d[2], rw = d[3];
-    if (y < rh && x < rw)
-      v = (float)s[(long)fs_resize_nearest(y, rh, sh) * Ws + fs_resize_nearest(x, rw, sw)];
-  }
-  out[(long)b * H * W + i] = v;
-}
-
 // -- host side ------------------------------------------------------------------------------------------------------
 struct Plan {
   int L;                                     // coarsest level index (levels actually used)
@@ -541,15 +514,5 @@ extern "C" int fs_motion_mask(const FsMotionMaskArgs* a, void* stream) {
   if ((long)a->H * a->W >= (1L << 31)) return FS_EINVAL;
   hipLaunchKernelGGL(of_motion_mask, dim3(nblk((long)a->H * a->W), a->B), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), *a);
-  return fs_launch_status();
-}
-
-extern "C" int fs_augment_masks(const uint8_t* src, const double* minv, const int32_t* dims, const int32_t* iplan,
-                                float* out, int B, int Hs, int Ws, int H, int W, void* stream) {
-  if (!src || !out || (minv != nullptr) == (dims != nullptr) || (minv && !iplan)) return FS_EINVAL;
-  if (B < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1) return FS_EINVAL;
-  if ((long)Hs * Ws >= (1L << 31) || (long)H * W >= (1L << 31)) return FS_EINVAL;
-  hipLaunchKernelGGL(of_augment_masks, dim3(nblk((long)H * W), B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     src, minv, dims, iplan, out, Hs, Ws, H, W);
   return fs_launch_status();
 }

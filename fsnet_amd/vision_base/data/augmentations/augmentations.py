@@ -724,76 +724,79 @@ class DeviceAugment(object):
             if np.any(om != 0) or np.any(osd != 1):
                 raise NotImplementedError("('original_image', i) is normalised with mean 0 / std 1")
 
-    def _collate_resize(self, samples, plans):
+    def _stack_frames(self, samples, plans, stage, zeroed, checked=True):
+        """the batch's raw frames in one uint8 [B, F, Hs, Ws, 3] buffer, sample b's in the top-left of its slab, and the
+        mean / std of ('image', first index) -> (src, Hs, Ws, mean, std).  zeroed: the slack around smaller frames
+        (ragged sizes, Pad2Shape's padding) is zero; a batch of equal frames may then stay uninitialised until the copy.
+        checked: the frames of a sample share the plan's size, ('original_image', i) is the same picture, one
+        Normalize serves the batch — the validation input has never asked for these."""
         B, F = len(samples), len(self.frame_idxs)
-        r0 = plans[0]["resize"]
-        # training use (Resize-based configs): the resize also feeds ('original_image', i) and the patched mask, and
-        # colour ops / a mirror may follow it
-        train = any((self.original_family, i) in r0["keys"] for i in self.frame_idxs) or bool(r0.get("gt_keys"))
-        if train:
-            return self._collate_resize_train(samples, plans)
-        Hs = max(p["resize"]["src_hw"][0] for p in plans)
-        Ws = max(p["resize"]["src_hw"][1] for p in plans)
-        src = torch.zeros(B, F, Hs, Ws, 3, dtype=torch.uint8)
+        Hs = max(p[stage]["src_hw"][0] for p in plans)
+        Ws = max(p[stage]["src_hw"][1] for p in plans)
+        ragged = any(tuple(p[stage]["src_hw"]) != (Hs, Ws) for p in plans)
+        # pageable here (collate may run in a DataLoader worker); the loader's pin_memory thread pins it
+        src = (torch.zeros if zeroed or ragged else torch.empty)(B, F, Hs, Ws, 3, dtype=torch.uint8)
         src_np = src.numpy()
-        dims = np.zeros((B, 4), dtype=np.int32)
         key0 = (self.image_family, self.frame_idxs[0])
         mean, std = plans[0]["normalize"].get(key0, (np.zeros(3, np.float32), np.ones(3, np.float32)))
         for b, (s, p) in enumerate(zip(samples, plans)):
-            r = p["resize"]
-            if p["warp"] is not None or p["ops"] or p["mirror"] or (r["out_h"], r["out_w"]) != (r0["out_h"], r0["out_w"]):
-                raise NotImplementedError("a validation batch is Resize + Normalize with one output size")
-            if p.get("gt_extra"):
-                raise NotImplementedError("ground-truth images %r travel with a training Resize (gt_image_keys), not "
-                                          "the validation input" % (p["gt_extra"],))
-            h, w = r["src_hw"]
-            for f, idx in enumerate(self.frame_idxs):
-                src_np[b, f, :h, :w] = s[(self.image_family, idx)]
-            # crop_1 keeps the left out_w columns of a wider resize; pads are zero rows / columns after it
-            dims[b] = (h, w, r["h"], r["w"])
-        batch = {PLAN: dict(src=src, dims=torch.from_numpy(dims), mean=mean, std=std, out_hw=(r0["out_h"], r0["out_w"]),
-                            kind="resize")}
-        self._collate_rest(samples, batch)
-        return batch
-
-    def _collate_resize_train(self, samples, plans):
-        B, F = len(samples), len(self.frame_idxs)
-        r0 = plans[0]["resize"]
-        Hs = max(p["resize"]["src_hw"][0] for p in plans)
-        Ws = max(p["resize"]["src_hw"][1] for p in plans)
-        src = torch.zeros(B, F, Hs, Ws, 3, dtype=torch.uint8)
-        src_np = src.numpy()
-        dims = np.zeros((B, 4), dtype=np.int32)
-        iplan = np.zeros((B, 8), dtype=np.int32)
-        fplan = np.zeros((B, 4), dtype=np.float32)
-        key0 = (self.image_family, self.frame_idxs[0])
-        mean, std = plans[0]["normalize"].get(key0, (np.zeros(3, np.float32), np.ones(3, np.float32)))
-        for b, (s, p) in enumerate(zip(samples, plans)):
-            r = p["resize"]
-            if p["warp"] is not None or p["hsv"] or (r["out_h"], r["out_w"]) != (r0["out_h"], r0["out_w"]):
-                raise NotImplementedError("a Resize-based training batch shares one output size and ends in RGB")
-            h, w = r["src_hw"]
+            h, w = _raw_hw(p, p[stage]["src_hw"])
             for f, idx in enumerate(self.frame_idxs):
                 frame = s[(self.image_family, idx)]
-                if frame.shape != (h, w, 3):
+                if checked and frame.shape != (h, w, 3):
                     raise ValueError("frames of one sample must share their size")
                 src_np[b, f, :h, :w] = frame
                 okey = (self.original_family, idx)
-                if okey in s and s[okey] is not frame and (
+                if checked and okey in s and s[okey] is not frame and (
                         s[okey].shape != frame.shape or not np.array_equal(s[okey][::16, ::16], frame[::16, ::16])):
                     raise ValueError("%r is expected to be the unaugmented copy of the image" % (okey,))
-            self._check_normalize(s, p, mean, std)
-            dims[b] = (h, w, r["h"], r["w"])
+            if checked:
+                self._check_normalize(s, p, mean, std)
+        return src, Hs, Ws, mean, std
+
+    def _colour_rows(self, plans):
+        iplan = np.zeros((len(plans), 8), dtype=np.int32)
+        fplan = np.zeros((len(plans), 4), dtype=np.float32)
+        for b, p in enumerate(plans):
             self._colour_plan(p, iplan[b], fplan[b])
-        batch = {PLAN: dict(src=src, dims=torch.from_numpy(dims), iplan=torch.from_numpy(iplan),
-                            fplan=torch.from_numpy(fplan), mean=mean, std=std, out_hw=(r0["out_h"], r0["out_w"]),
-                            kind="resize", train=True, mask='patched_mask' in r0.get("gt_keys", []))}
-        if not batch[PLAN]["mask"] and any(p.get("patched_mask") is not None for p in plans):
-            raise ValueError("samples of one batch must carry the same ground-truth images")
-        self._collate_mask(plans, batch, Hs, Ws, "resize")
-        self._collate_gt(samples, plans, batch)
+        return iplan, fplan
+
+    def _finish(self, samples, plans, plan, Hs, Ws, stage, gt=True):
+        """the collated batch around one plan: the patched-mask plane and the extra ground-truth images (training
+        plans), then every other key of the samples"""
+        batch = {PLAN: plan}
+        if gt:
+            self._collate_mask(plans, batch, Hs, Ws, stage)
+            self._collate_gt(samples, plans, batch)
         self._collate_rest(samples, batch)
         return batch
+
+    def _collate_resize(self, samples, plans):
+        r0 = plans[0]["resize"]
+        out_hw = (r0["out_h"], r0["out_w"])
+        # training use (Resize-based configs): the resize also feeds ('original_image', i) and the patched mask, and
+        # colour ops / a mirror may follow it
+        train = any((self.original_family, i) in r0["keys"] for i in self.frame_idxs) or bool(r0.get("gt_keys"))
+        for p in plans:
+            r = p["resize"]
+            if train and (p["warp"] is not None or p["hsv"] or (r["out_h"], r["out_w"]) != out_hw):
+                raise NotImplementedError("a Resize-based training batch shares one output size and ends in RGB")
+            if not train and (p["warp"] is not None or p["ops"] or p["mirror"] or (r["out_h"], r["out_w"]) != out_hw):
+                raise NotImplementedError("a validation batch is Resize + Normalize with one output size")
+            if not train and p.get("gt_extra"):
+                raise NotImplementedError("ground-truth images %r travel with a training Resize (gt_image_keys), not "
+                                          "the validation input" % (p["gt_extra"],))
+        src, Hs, Ws, mean, std = self._stack_frames(samples, plans, "resize", True, checked=train)
+        # crop_1 keeps the left out_w columns of a wider resize; pads are zero rows / columns after it
+        dims = np.array([tuple(p["resize"]["src_hw"]) + (p["resize"]["h"], p["resize"]["w"]) for p in plans], np.int32)
+        plan = dict(src=src, dims=torch.from_numpy(dims), mean=mean, std=std, out_hw=out_hw, kind="resize")
+        if train:
+            iplan, fplan = self._colour_rows(plans)
+            plan.update(iplan=torch.from_numpy(iplan), fplan=torch.from_numpy(fplan), train=True,
+                        mask='patched_mask' in r0.get("gt_keys", []))
+            if not plan["mask"] and any(p.get("patched_mask") is not None for p in plans):
+                raise ValueError("samples of one batch must carry the same ground-truth images")
+        return self._finish(samples, plans, plan, Hs, Ws, "resize", gt=train)
 
     # -- plans the launches above cannot express: an output window, a padded source, the op list, a Copy split -----
     @staticmethod
@@ -829,7 +832,7 @@ class DeviceAugment(object):
         return len(cls._op_slots(p)[0]) != 0
 
     def _collate_ext(self, samples, plans):
-        B, F = len(samples), len(self.frame_idxs)
+        B = len(samples)
         warp = plans[0]["warp"] is not None
         stage = "warp" if warp else "resize"
         sizes = set()
@@ -843,15 +846,9 @@ class DeviceAugment(object):
         if len(sizes) != 1:
             raise ValueError("samples of one batch must share the output size, got %s" % sorted(sizes))
         out_h, out_w = sizes.pop()
-        Hs = max(p[stage]["src_hw"][0] for p in plans)
-        Ws = max(p[stage]["src_hw"][1] for p in plans)
-        src = torch.zeros(B, F, Hs, Ws, 3, dtype=torch.uint8)       # zeros: ragged frames and Pad2Shape's padding
-        src_np = src.numpy()
         dims = np.zeros((B, 4), dtype=np.int32)
         win = np.zeros((B, 8), dtype=np.int32)
         minv = np.zeros((B, 6), dtype=np.float64) if warp else None
-        key0 = (self.image_family, self.frame_idxs[0])
-        mean, std = plans[0]["normalize"].get(key0, (np.zeros(3, np.float32), np.ones(3, np.float32)))
         slots = [self._op_slots(p) for p in plans]
         split = max(len(b) for b, _ in slots)
         n_ops = split + max(len(a) for _, a in slots)
@@ -860,19 +857,9 @@ class DeviceAugment(object):
                 n_ops, MAX_OPS))
         codes = np.full((B, MAX_OPS), 4, dtype=np.int32)            # 4: nothing
         vals = np.zeros((B, MAX_OPS, 3), dtype=np.float64)
-        for b, (s, p) in enumerate(zip(samples, plans)):
+        src, Hs, Ws, mean, std = self._stack_frames(samples, plans, stage, True)
+        for b, p in enumerate(plans):
             st = p[stage]
-            h, w = _raw_hw(p, st["src_hw"])
-            for f, idx in enumerate(self.frame_idxs):
-                frame = s[(self.image_family, idx)]
-                if frame.shape != (h, w, 3):
-                    raise ValueError("frames of one sample must share their size")
-                src_np[b, f, :h, :w] = frame
-                okey = (self.original_family, idx)
-                if okey in s and s[okey] is not frame and (
-                        s[okey].shape != frame.shape or not np.array_equal(s[okey][::16, ::16], frame[::16, ::16])):
-                    raise ValueError("%r is expected to be the unaugmented copy of the image" % (okey,))
-            self._check_normalize(s, p, mean, std)
             if warp:
                 minv[b] = invert_affine(st["M"])
                 dims[b] = (st["src_hw"][0], st["src_hw"][1], 0, 0)
@@ -891,13 +878,10 @@ class DeviceAugment(object):
         with_mask = warp or 'patched_mask' in plans[0][stage].get("gt_keys", [])
         if not with_mask and any(p.get("patched_mask") is not None for p in plans):
             raise ValueError("samples of one batch must carry the same ground-truth images")
-        batch = {PLAN: dict(src=src, dims=torch.from_numpy(dims), win=torch.from_numpy(win), codes=torch.from_numpy(codes),
-                            vals=torch.from_numpy(vals), minv=torch.from_numpy(minv) if warp else None, n_ops=n_ops,
-                            split=split, mean=mean, std=std, out_hw=(out_h, out_w), kind="ext", mask=with_mask)}
-        self._collate_mask(plans, batch, Hs, Ws, stage)
-        self._collate_gt(samples, plans, batch)
-        self._collate_rest(samples, batch)
-        return batch
+        plan = dict(src=src, dims=torch.from_numpy(dims), win=torch.from_numpy(win), codes=torch.from_numpy(codes),
+                    vals=torch.from_numpy(vals), minv=torch.from_numpy(minv) if warp else None, n_ops=n_ops,
+                    split=split, mean=mean, std=std, out_hw=(out_h, out_w), kind="ext", mask=with_mask)
+        return self._finish(samples, plans, plan, Hs, Ws, stage)
 
     @staticmethod
     def _collate_mask(plans, batch, Hs, Ws, stage):
@@ -946,8 +930,26 @@ class DeviceAugment(object):
             else:
                 batch[key] = vals
 
+    def _collate_warp(self, samples, plans):
+        for p in plans:
+            if p["warp"] is None:
+                raise ValueError("samples of one batch must share the resampling stage")
+            if p["hsv"]:
+                raise ValueError("pipeline ended in HSV")
+        w0 = plans[0]["warp"]
+        for p in plans:
+            if (p["warp"]["out_w"], p["warp"]["out_h"]) != (w0["out_w"], w0["out_h"]):
+                raise ValueError("samples of one batch must share the output size")
+        # equal frames fill the buffer completely: no 50 MB memset per batch at the training shape
+        src, Hs, Ws, mean, std = self._stack_frames(samples, plans, "warp", False)
+        iplan, fplan = self._colour_rows(plans)
+        iplan[:, 5:7] = [p["warp"]["src_hw"] for p in plans]
+        minv = np.stack([invert_affine(p["warp"]["M"]) for p in plans])
+        plan = dict(src=src, minv=torch.from_numpy(minv), iplan=torch.from_numpy(iplan), fplan=torch.from_numpy(fplan),
+                    mean=mean, std=std, out_hw=(w0["out_h"], w0["out_w"]), kind="warp")
+        return self._finish(samples, plans, plan, Hs, Ws, "warp")
+
     def collate(self, samples):
-        B, F = len(samples), len(self.frame_idxs)
         plans = [s[PLAN] for s in samples]
         for s, p in zip(samples, plans):
             if _stage(p) is None:       # a chain without RandomWarpAffine / Resize runs as a resize onto itself
@@ -957,159 +959,85 @@ class DeviceAugment(object):
             return self._collate_ext(samples, plans)
         if plans[0].get("resize") is not None:
             return self._collate_resize(samples, plans)
-        for p in plans:
-            if p["warp"] is None:
-                raise ValueError("samples of one batch must share the resampling stage")
-            if p["hsv"]:
-                raise ValueError("pipeline ended in HSV")
-        w0 = plans[0]["warp"]
-        out_w, out_h = w0["out_w"], w0["out_h"]
-        Hs = max(p["warp"]["src_hw"][0] for p in plans)
-        Ws = max(p["warp"]["src_hw"][1] for p in plans)
-        ragged = any(p["warp"]["src_hw"] != (Hs, Ws) for p in plans)
-        # pageable here (collate may run in a DataLoader worker); the loader's pin_memory thread pins it
-        src = (torch.zeros if ragged else torch.empty)(B, F, Hs, Ws, 3, dtype=torch.uint8)
-        src_np = src.numpy()
-        minv = np.zeros((B, 6), dtype=np.float64)
-        iplan = np.zeros((B, 8), dtype=np.int32)
-        fplan = np.zeros((B, 4), dtype=np.float32)
-        img_key0 = (self.image_family, self.frame_idxs[0])
-        mean, std = plans[0]["normalize"].get(img_key0, (np.zeros(3, np.float32), np.ones(3, np.float32)))
-        for b, (s, p) in enumerate(zip(samples, plans)):
-            h, w = p["warp"]["src_hw"]
-            if (p["warp"]["out_w"], p["warp"]["out_h"]) != (out_w, out_h):
-                raise ValueError("samples of one batch must share the output size")
-            for f, idx in enumerate(self.frame_idxs):
-                frame = s[(self.image_family, idx)]
-                if frame.shape != (h, w, 3):
-                    raise ValueError("frames of one sample must share their size")
-                src_np[b, f, :h, :w] = frame
-                okey = (self.original_family, idx)
-                if okey in s and s[okey] is not frame and (
-                        s[okey].shape != frame.shape or not np.array_equal(s[okey][::16, ::16], frame[::16, ::16])):
-                    raise ValueError("%r is expected to be the unaugmented copy of the image" % (okey,))
-            self._check_normalize(s, p, mean, std)
-            minv[b] = invert_affine(p["warp"]["M"])
-            self._colour_plan(p, iplan[b], fplan[b])
-            iplan[b, 5], iplan[b, 6] = h, w
-        batch = {PLAN: dict(src=src, minv=torch.from_numpy(minv), iplan=torch.from_numpy(iplan),
-                            fplan=torch.from_numpy(fplan), mean=mean, std=std, out_hw=(out_h, out_w), kind="warp")}
-        self._collate_mask(plans, batch, Hs, Ws, "warp")
-        self._collate_gt(samples, plans, batch)
-        self._collate_rest(samples, batch)
-        return batch
+        return self._collate_warp(samples, plans)
 
     # -- device side -------------------------------------------------------------------------------
+    _UPLOADS = ("src", "mask_src", "minv", "iplan", "fplan", "dims", "win", "codes", "vals")
+
     def materialize(self, batch, device=None):
-        from ....hip.binding import lib, check, stream_ptr, FsAugArgs, FsResizeArgs
+        from ....hip.binding import lib, check, stream_ptr, FsAugArgs, FsResizeArgs, FsAugExtArgs
         device = torch.device(device or self.device or "cuda")
         plan = batch.pop(PLAN)
-        src = plan["src"].to(device, non_blocking=True)
-        B, F, Hs, Ws, _ = src.shape
-        H, W = plan["out_hw"]
-        mask_src = plan["mask_src"].to(device, non_blocking=True) if plan.get("mask_src") is not None else None
-        if plan["kind"] == "ext":
-            from ....hip.binding import FsAugExtArgs
-            from ....hip import ops
-            up = {k: plan[k].to(device, non_blocking=True) for k in ("dims", "win", "codes", "vals")}
-            minv = plan["minv"].to(device, non_blocking=True) if plan["minv"] is not None else None
-            image = torch.empty(F, B, 3, H, W, dtype=torch.float32, device=device)
-            original = torch.empty(F, B, 3, H, W, dtype=torch.float32, device=device) if self.original_family else None
-            mask = torch.empty(B, H, W, dtype=torch.float64, device=device) if plan["mask"] and self.mask_key else None
-            x = FsAugExtArgs()
-            x.src, x.dims, x.win, x.ops, x.opv = (src.data_ptr(), up["dims"].data_ptr(), up["win"].data_ptr(),
-                                                  up["codes"].data_ptr(), up["vals"].data_ptr())
-            x.minv = minv.data_ptr() if minv is not None else None
-            x.image = image.data_ptr()
-            x.original = original.data_ptr() if original is not None else None
-            x.mask = mask.data_ptr() if mask is not None else None
-            x.mask_src = mask_src.data_ptr() if mask_src is not None and mask is not None else None
+        up = {k: plan[k].to(device, non_blocking=True) for k in self._UPLOADS if plan.get(k) is not None}
+
+        def ptr(key):
+            return up[key].data_ptr() if key in up else None
+
+        def outputs(args, original, mask):
+            """the launch's results, bound to the argument struct (with the mean / std and the sizes every struct has)
+            and to the batch's keys"""
+            B, F, Hs, Ws, _ = up["src"].shape
+            H, W = plan["out_hw"]
+            args.B, args.F, args.Hs, args.Ws, args.H, args.W = B, F, Hs, Ws, H, W
             for k in range(3):
-                x.mean[k], x.std[k] = float(plan["mean"][k]), float(plan["std"][k])
-            x.B, x.F, x.Hs, x.Ws, x.H, x.W, x.n_ops, x.split = B, F, Hs, Ws, H, W, plan["n_ops"], plan["split"]
-            if minv is not None:
+                args.mean[k], args.std[k] = float(plan["mean"][k]), float(plan["std"][k])
+            image = torch.empty(F, B, 3, H, W, dtype=torch.float32, device=device)
+            original = torch.empty(F, B, 3, H, W, dtype=torch.float32, device=device) if original else None
+            mask = torch.empty(B, H, W, dtype=torch.float64, device=device) if mask else None
+            args.src, args.image = ptr("src"), image.data_ptr()
+            args.original = original.data_ptr() if original is not None else None
+            args.mask = mask.data_ptr() if mask is not None else None
+            for f, idx in enumerate(self.frame_idxs):
+                batch[(self.image_family, idx)] = image[f]
+                if original is not None:
+                    batch[(self.original_family, idx)] = original[f]
+            if mask is not None:
+                batch[self.mask_key] = mask
+            return args
+
+        if plan["kind"] == "ext":
+            x = outputs(FsAugExtArgs(), self.original_family, plan["mask"] and self.mask_key)
+            x.dims, x.win, x.ops, x.opv, x.minv = ptr("dims"), ptr("win"), ptr("codes"), ptr("vals"), ptr("minv")
+            x.mask_src = ptr("mask_src") if x.mask else None
+            x.n_ops, x.split = plan["n_ops"], plan["split"]
+            if "minv" in up:
                 check(lib.fs_augment_frames_ext(C.byref(x), stream_ptr()), "augment_frames_ext")
             else:
                 check(lib.fs_resize_frames_ext(C.byref(x), stream_ptr()), "resize_frames_ext")
-            for f, idx in enumerate(self.frame_idxs):
-                batch[(self.image_family, idx)] = image[f]
-                if original is not None:
-                    batch[(self.original_family, idx)] = original[f]
-            if mask is not None:
-                batch[self.mask_key] = mask
-            for key, g in (plan.get("gt") or {}).items():
-                batch[key] = ops.augment_masks_ext(g.to(device, non_blocking=True), H, W, up["dims"], up["win"], minv=minv)
-            for key, val in list(batch.items()):
-                if isinstance(val, torch.Tensor) and not val.is_cuda:
-                    batch[key] = val.to(device, non_blocking=True)
-            return batch
-        if plan["kind"] == "resize":
-            dims = plan["dims"].to(device, non_blocking=True)
-            image = torch.empty(F, B, 3, H, W, dtype=torch.float32, device=device)
-            r = FsResizeArgs()
-            r.src, r.dims, r.image = src.data_ptr(), dims.data_ptr(), image.data_ptr()
-            for k in range(3):
-                r.mean[k], r.std[k] = float(plan["mean"][k]), float(plan["std"][k])
-            r.B, r.F, r.Hs, r.Ws, r.H, r.W = B, F, Hs, Ws, H, W
-            original = mask = None
-            if plan.get("train"):
-                iplan = plan["iplan"].to(device, non_blocking=True)
-                fplan = plan["fplan"].to(device, non_blocking=True)
-                original = torch.empty(F, B, 3, H, W, dtype=torch.float32, device=device)
-                r.iplan, r.fplan, r.original = iplan.data_ptr(), fplan.data_ptr(), original.data_ptr()
-                if plan.get("mask"):
-                    mask = torch.empty(B, H, W, dtype=torch.float64, device=device)
-                    r.mask = mask.data_ptr()
-            if mask_src is not None:
-                check(lib.fs_resize_frames_masked(C.byref(r), mask_src.data_ptr(), stream_ptr()), "resize_masked")
+        elif plan["kind"] == "resize":
+            r = outputs(FsResizeArgs(), plan.get("train"), plan.get("train") and plan.get("mask"))
+            r.dims, r.iplan, r.fplan = ptr("dims"), ptr("iplan"), ptr("fplan")
+            if "mask_src" in up:
+                check(lib.fs_resize_frames_masked(C.byref(r), ptr("mask_src"), stream_ptr()), "resize_masked")
             else:
                 check(lib.fs_resize_frames(C.byref(r), stream_ptr()), "resize_frames")
-            for f, idx in enumerate(self.frame_idxs):
-                batch[(self.image_family, idx)] = image[f]
-                if original is not None:
-                    batch[(self.original_family, idx)] = original[f]
-            if mask is not None:
-                batch[self.mask_key] = mask
-            self._materialize_gt(plan, batch, device, H, W, dims=dims, iplan=plan.get("train") and iplan)
-            for key, val in list(batch.items()):
-                if isinstance(val, torch.Tensor) and not val.is_cuda:
-                    batch[key] = val.to(device, non_blocking=True)
-            return batch
-        minv = plan["minv"].to(device, non_blocking=True)
-        iplan = plan["iplan"].to(device, non_blocking=True)
-        fplan = plan["fplan"].to(device, non_blocking=True)
-        image = torch.empty(F, B, 3, H, W, dtype=torch.float32, device=device)
-        original = torch.empty(F, B, 3, H, W, dtype=torch.float32, device=device)
-        mask = torch.empty(B, H, W, dtype=torch.float64, device=device)
-        a = FsAugArgs()
-        a.src, a.minv, a.iplan, a.fplan = src.data_ptr(), minv.data_ptr(), iplan.data_ptr(), fplan.data_ptr()
-        a.image, a.original, a.mask = image.data_ptr(), original.data_ptr(), mask.data_ptr()
-        for k in range(3):
-            a.mean[k], a.std[k] = float(plan["mean"][k]), float(plan["std"][k])
-        a.B, a.F, a.Hs, a.Ws, a.H, a.W = B, F, Hs, Ws, H, W
-        if mask_src is not None:
-            check(lib.fs_augment_frames_masked(C.byref(a), mask_src.data_ptr(), stream_ptr()), "augment_masked")
         else:
-            check(lib.fs_augment_frames(C.byref(a), stream_ptr()), "augment_frames")
-        for f, idx in enumerate(self.frame_idxs):
-            batch[(self.image_family, idx)] = image[f]
-            batch[(self.original_family, idx)] = original[f]
-        batch[self.mask_key] = mask
-        self._materialize_gt(plan, batch, device, H, W, minv=minv, iplan=iplan)
+            a = outputs(FsAugArgs(), True, True)
+            a.minv, a.iplan, a.fplan = ptr("minv"), ptr("iplan"), ptr("fplan")
+            if "mask_src" in up:
+                check(lib.fs_augment_frames_masked(C.byref(a), ptr("mask_src"), stream_ptr()), "augment_masked")
+            else:
+                check(lib.fs_augment_frames(C.byref(a), stream_ptr()), "augment_frames")
+        self._materialize_gt(plan, batch, up, device)
         for key, val in list(batch.items()):
             if isinstance(val, torch.Tensor) and not val.is_cuda:
                 batch[key] = val.to(device, non_blocking=True)
         return batch
 
     @staticmethod
-    def _materialize_gt(plan, batch, device, H, W, minv=None, dims=None, iplan=None):
-        """each extra ground-truth image through the frames' warp / resize and mirror: fp32 [B, H, W] on the device"""
+    def _materialize_gt(plan, batch, up, device):
+        """each extra ground-truth image through the frames' warp / resize and mirror or window: fp32 [B, H, W] on the
+        device"""
         if not plan.get("gt"):
             return
         from ....hip import ops
+        H, W = plan["out_hw"]
         for key, src in plan["gt"].items():
-            batch[key] = ops.augment_masks(src.to(device, non_blocking=True), H, W, minv=minv, dims=dims,
-                                           iplan=iplan if iplan is not None and iplan is not False else None)
+            src = src.to(device, non_blocking=True)
+            if "win" in up:
+                batch[key] = ops.augment_masks_ext(src, H, W, up["dims"], up["win"], minv=up.get("minv"))
+            else:
+                batch[key] = ops.augment_masks(src, H, W, minv=up.get("minv"), dims=up.get("dims"), iplan=up.get("iplan"))
 
     def __call__(self, samples, device=None):
         return self.materialize(self.collate(samples), device)

@@ -170,6 +170,19 @@ def test_new_launches_equal_the_old_ones_on_plans_both_express(dev, golden, tag)
     for f, i in enumerate(HX.FRAME_IDXS):
         assert torch.equal(t["image"][f], want[("image", i)]) and torch.equal(t["original"][f], want[("original_image", i)])
     assert torch.equal(t["mask"], want["patched_mask"])
+    # one ground-truth plane through the masks entry point of either family
+    from fsnet_amd.hip import ops
+    B, _, Hs, Ws, _ = plan["src"].shape
+    plane = _t(np.random.RandomState(5).randint(0, 2, size=(B, Hs, Ws)).astype(np.uint8), dev)
+    H, W = plan["out_hw"]
+    iplan = plan["iplan"].to(dev)
+    if tag == "a":
+        old = ops.augment_masks(plane, H, W, minv=t["minv"], iplan=iplan)
+    else:
+        old = ops.augment_masks(plane, H, W, dims=plan["dims"].to(dev), iplan=iplan)
+    new = ops.augment_masks_ext(plane, H, W, t["dims"], t["win"], minv=t.get("minv"))
+    torch.cuda.synchronize()
+    assert torch.equal(old, new) and 0.0 < float(new.mean()) < 1.0
     flips = plan["iplan"][:, 4]
     assert 0 < int(flips.sum()) < len(flips)
 

@@ -219,16 +219,20 @@ def test_abi_rejects_invalid_parameters_without_a_gpu():
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"),
                     reason="hipcc not available")
 def test_optflow_kernels_do_not_spill():
+    """optflow.hip's eight kernels, and the masks kernel that carries their result through the input pipeline beside
+    the four frames kernels of augment.hip"""
     from fsnet_amd.csrc import build as B
-    src = os.path.join(os.path.dirname(B.__file__), "optflow.hip")
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "k.s")
-        flags = [f for f in B.FLAGS if f != "-fPIC"] + B.extra_flags(src)
-        subprocess.run([B.HIPCC] + flags + ["-S", "--cuda-device-only", src, "-o", out], check=True,
-                       stderr=subprocess.DEVNULL)
-        txt = open(out).read()
-    kernels = re.findall(r"^\s*\.amdhsa_kernel (\S+)", txt, re.M)
-    assert len(kernels) == 9
-    assert max(int(x) for x in re.findall(r"^\s*\.vgpr_spill_count:\s*(\d+)", txt, re.M)) == 0
-    assert max(int(x) for x in re.findall(r"^; ScratchSize: (\d+)", txt, re.M)) == 0
-    assert not re.search(r"^\s*scratch_(load|store)", txt, re.M)
+    for name, count in (("optflow.hip", 8), ("augment.hip", 5)):
+        src = os.path.join(os.path.dirname(B.__file__), name)
+        with tempfile.TemporaryDirectory() as d:
+            out = os.path.join(d, "k.s")
+            flags = [f for f in B.FLAGS if f != "-fPIC"] + B.extra_flags(src)
+            subprocess.run([B.HIPCC] + flags + ["-S", "--cuda-device-only", src, "-o", out], check=True,
+                           stderr=subprocess.DEVNULL)
+            txt = open(out).read()
+        kernels = re.findall(r"^\s*\.amdhsa_kernel (\S+)", txt, re.M)
+        assert len(kernels) == count, name
+        assert any("masks_kernel" in k for k in kernels) == (name == "augment.hip")
+        assert max(int(x) for x in re.findall(r"^\s*\.vgpr_spill_count:\s*(\d+)", txt, re.M)) == 0, name
+        assert max(int(x) for x in re.findall(r"^; ScratchSize: (\d+)", txt, re.M)) == 0, name
+        assert not re.search(r"^\s*scratch_(load|store)", txt, re.M), name

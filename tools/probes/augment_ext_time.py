@@ -4,6 +4,9 @@ batch 12 x 3 frames of 375x1242 uint8 -> 192x640.  HIP events around each launch
   ext    fs_augment_frames_ext on the same plan (full-canvas window, the same three ops, split 0)
   ext_e  fs_augment_frames_ext with the op list of the tests' case e (brightness, HSV with hue and saturation,
          eigenvalue noise, contrast | Copy | brightness: five slots, split 4, an f64 tail)
+  resize      fs_resize_frames in its training form (plan rows, original, mask), the frames resized to the output
+  resize_ext  fs_resize_frames_ext on the same plan
+  masks       fs_augment_masks, one uint8 plane per sample through the warp's plan
 Prints one JSON line.
     python tools/probes/augment_ext_time.py [--iters 50]"""
 import argparse
@@ -16,7 +19,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-from fsnet_amd.hip.binding import lib, check, stream_ptr, FsAugArgs, FsAugExtArgs  # noqa: E402
+from fsnet_amd.hip.binding import lib, check, stream_ptr, FsAugArgs, FsAugExtArgs, FsResizeArgs  # noqa: E402
 
 
 def median_us(launch, iters):
@@ -81,6 +84,25 @@ def main():
     out["ext_equals_old"] = bool(torch.equal(image, want))
     x.ops, x.opv, x.n_ops, x.split = t["codes_e"].data_ptr(), t["vals_e"].data_ptr(), 5, 4
     out["ext_e_us"] = median_us(lambda: check(lib.fs_augment_frames_ext(C.byref(x), stream_ptr()), "ext_e"), args.iters)
+    rdims = torch.from_numpy(np.tile(np.array([Hs, Ws, H, W], np.int32), (B, 1))).to(dev)
+    r = FsResizeArgs()
+    r.src, r.dims, r.iplan, r.fplan = src.data_ptr(), rdims.data_ptr(), t["iplan"].data_ptr(), t["fplan"].data_ptr()
+    r.image, r.original, r.mask = image.data_ptr(), orig.data_ptr(), mask.data_ptr()
+    for k in range(3):
+        r.mean[k], r.std[k] = mean[k], std[k]
+    r.B, r.F, r.Hs, r.Ws, r.H, r.W = B, F, Hs, Ws, H, W
+    out["resize_us"] = median_us(lambda: check(lib.fs_resize_frames(C.byref(r), stream_ptr()), "resize"), args.iters)
+    want = image.clone()
+    x.minv, x.dims = None, rdims.data_ptr()
+    x.ops, x.opv, x.n_ops, x.split = t["codes3"].data_ptr(), t["vals3"].data_ptr(), 3, 0
+    out["resize_ext_us"] = median_us(lambda: check(lib.fs_resize_frames_ext(C.byref(x), stream_ptr()), "resize_ext"),
+                                     args.iters)
+    out["resize_ext_equals_old"] = bool(torch.equal(image, want))
+    plane = torch.from_numpy(rs.randint(0, 2, size=(B, Hs, Ws)).astype(np.uint8)).to(dev)
+    warped = torch.empty(B, H, W, device=dev)
+    out["masks_us"] = median_us(lambda: check(lib.fs_augment_masks(
+        plane.data_ptr(), t["minv"].data_ptr(), None, t["iplan"].data_ptr(), warped.data_ptr(), B, Hs, Ws, H, W,
+        stream_ptr()), "masks"), args.iters)
     out = {k: round(v, 1) if isinstance(v, float) else v for k, v in out.items()}
     out["workload"] = "B=%d x %d frames %dx%d u8 -> %dx%d, median of %d" % (B, F, Hs, Ws, H, W, args.iters)
     print(json.dumps(out))
