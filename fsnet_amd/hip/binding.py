@@ -243,6 +243,17 @@ class FsDcnArgs(C.Structure):
     ]
 
 
+FS_CAT_MAX = 8
+
+
+class FsCatArgs(C.Structure):
+    _fields_ = [
+        ("part", C.c_void_p * 8), ("wide", C.c_void_p), ("M", C.c_int64),
+        ("C", C.c_int32 * 8), ("off", C.c_int32 * 8), ("accumulate", C.c_int32 * 8),
+        ("Ctot", C.c_int32), ("n", C.c_int32),
+    ]
+
+
 ABI_VERSION = 15    # FS_ABI_VERSION of include/fsnet_hip.h (tests/test_abi.py holds the two together)
 _lib = None
 

@@ -6,7 +6,7 @@ import os
 import torch
 from torch.nn.modules.utils import _pair
 
-from .binding import (lib, check, stream_ptr, FsBnApplyArgs, FsBnBwdArgs, FsDcnArgs, FsDistillUnscaledArgs, FsFlowArgs,
+from .binding import (lib, check, stream_ptr, FS_CAT_MAX, FsBnApplyArgs, FsBnBwdArgs, FsCatArgs, FsDcnArgs, FsDistillUnscaledArgs, FsFlowArgs,
                       FsMotionMaskArgs, FsPhotoArgs, FsPhotoMeiMultiArgs, FsPhotoMultiArgs, FsPostOptArgs, FsSmoothArgs)
 from .conv import dtype_code, roundup, _timed, BN_EPS, BN_MOMENTUM, Spec, run_specs
 
@@ -1525,3 +1525,78 @@ def dcn_backward_weight(g, x, offset, mask, dy, want_bias=False, dw=None, d_bias
     a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
     check(lib.fs_dcn_bwd_weight(C.byref(a), g.code, stream_ptr()), "dcn_bwd_weight")
     return dw, d_bias
+
+
+# ---------------------------------------------------------------------------------- DLA backbone (dla.hip)
+def _pixel_stride(t):
+    """elements between neighbouring pixels of an NHWC view whose pixels are evenly spaced: a dense tensor, or a channel
+    slice of one (the strides torch reports for dimensions of size 1 mean nothing and are not looked at)"""
+    N, H, W, Cc = t.shape
+    if t.is_contiguous():
+        return Cc
+    pix = t.stride(2) if W > 1 else (t.stride(1) if H > 1 else t.stride(0))
+    assert t.stride(3) == 1 and pix >= Cc
+    assert (H == 1 or t.stride(1) == W * pix) and (N == 1 or t.stride(0) == H * W * pix)
+    return pix
+
+
+def pool2_fwd(x, out=None):
+    """nn.MaxPool2d(2, stride=2) of dense NHWC x -> (y, idx).  out: a [N,H/2,W/2,C] view with contiguous channels whose
+    pixels are evenly spaced (a channel slice of a wider dense buffer) that receives y instead of a fresh tensor."""
+    N, H, W, Cc = x.shape
+    assert x.is_contiguous()
+    Ho, Wo = H // 2, W // 2
+    if out is None:
+        out = torch.empty(N, Ho, Wo, Cc, dtype=x.dtype, device=x.device)
+    assert out.shape == (N, Ho, Wo, Cc) and out.dtype == x.dtype
+    pix = _pixel_stride(out)
+    idx = torch.empty(N, Ho, Wo, Cc, dtype=torch.uint8, device=x.device)
+    _timed("pool2_fwd", x.numel() * x.element_size() * 1.25 + idx.numel(),
+           lambda: check(lib.fs_pool2_fwd(x.data_ptr(), out.data_ptr(), idx.data_ptr(), N, H, W, Cc, pix, 0,
+                                          dtype_code(x.dtype), stream_ptr()), "pool2_fwd"), tag=str(tuple(x.shape)))
+    return out, idx
+
+
+def pool2_bwd(dy, idx, H, W, addend=None):
+    """gradient of pool2_fwd's input (+ addend, dense like it); dy may be a channel slice of a wider dense buffer"""
+    N, Ho, Wo, Cc = dy.shape
+    pix = _pixel_stride(dy)
+    assert idx.is_contiguous() and idx.shape == dy.shape and H == 2 * Ho and W == 2 * Wo
+    assert addend is None or (addend.is_contiguous() and addend.shape == (N, H, W, Cc) and addend.dtype == dy.dtype)
+    dx = torch.empty(N, H, W, Cc, dtype=dy.dtype, device=dy.device)
+    _timed("pool2_bwd", dx.numel() * dx.element_size() * (1.25 + (addend is not None)) + idx.numel(),
+           lambda: check(lib.fs_pool2_bwd(dy.data_ptr(), idx.data_ptr(), _p(addend), dx.data_ptr(), N, H, W, Cc, pix, 0,
+                                          dtype_code(dy.dtype), stream_ptr()), "pool2_bwd"), tag=str(tuple(dx.shape)))
+    return dx
+
+
+def _cat_args(wide, parts, offs, widths, accumulate):
+    a = FsCatArgs()
+    assert wide.is_contiguous() and len(parts) == len(offs) == len(widths)
+    a.wide, a.Ctot, a.M, a.n = wide.data_ptr(), wide.shape[-1], wide.numel() // wide.shape[-1], len(parts)
+    for i, (t, o, c) in enumerate(zip(parts, offs, widths)):
+        if i >= FS_CAT_MAX:
+            break                    # (the library refuses n > FS_CAT_MAX)
+        assert t is None or (t.is_contiguous() and t.shape[-1] == c and t.numel() == a.M * c and t.dtype == wide.dtype)
+        a.part[i], a.off[i], a.C[i] = _p(t), o, c
+        a.accumulate[i] = int(bool(accumulate[i])) if accumulate is not None else 0
+    return a
+
+
+def cat_fwd(wide, parts, offs, widths):
+    """channel slices [offs[i], offs[i] + widths[i]) of dense NHWC `wide` <- dense parts[i] (None: already there), ONE
+    launch for up to FS_CAT_MAX parts"""
+    a = _cat_args(wide, parts, offs, widths, None)
+    nb = 2 * sum(t.numel() for t in parts if t is not None) * wide.element_size()
+    _timed("cat_fwd", nb, lambda: check(lib.fs_cat_fwd(C.byref(a), dtype_code(wide.dtype), stream_ptr()), "cat_fwd"),
+           tag=str(tuple(wide.shape)))
+    return wide
+
+
+def cat_bwd(wide, parts, offs, widths, accumulate=None):
+    """dense parts[i] = (accumulate[i]: +=) channel slice i of `wide` (None: skipped), ONE launch"""
+    a = _cat_args(wide, parts, offs, widths, accumulate)
+    nb = sum(t.numel() * (2 + bool(accumulate and accumulate[i])) for i, t in enumerate(parts) if t is not None) * wide.element_size()
+    _timed("cat_bwd", nb, lambda: check(lib.fs_cat_bwd(C.byref(a), dtype_code(wide.dtype), stream_ptr()), "cat_bwd"),
+           tag=str(tuple(wide.shape)))
+    return parts

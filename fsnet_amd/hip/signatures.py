@@ -143,6 +143,11 @@ SIGNATURES = {
     "fs_dcn_workspace_bytes": (C.c_int64, [P, I]),
     "fs_dcn_tile": (C.c_int, [I, P, P]),
     "fs_dcn_fwd_channels": (C.c_int, [P, I]),
+    # added under ABI 15: the DLA backbone's 2x2 max pool and Root concatenation (FsCatArgs; dla.py:167, 207-208)
+    "fs_pool2_fwd": (C.c_int, [P, P, P, I, I, I, I, L, L, I, P]),
+    "fs_pool2_bwd": (C.c_int, [P, P, P, P, I, I, I, I, L, L, I, P]),
+    "fs_cat_fwd": (C.c_int, [P, I, P]),
+    "fs_cat_bwd": (C.c_int, [P, I, P]),
 }
 
 

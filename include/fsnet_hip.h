@@ -1072,6 +1072,37 @@ int fs_dcn_tile(int which, int32_t* pixels, int32_t* channels);
  * than 256 blocks would run; -1 for arguments fs_dcn_fwd would refuse */
 int fs_dcn_fwd_channels(const FsDcnArgs* args, int dtype);
 
+/* Added under ABI 15: what the DLA backbone (vision_base/networks/models/backbone/dla.py) needs beside the convolution
+ * and BatchNorm launches — Tree.downsample and Root's torch.cat (dla.py:167, 207-208).  NHWC in the compute dtype, every
+ * channel count and channel offset a whole number of 16-byte vectors (8 bf16 / 4 fp32), every pointer 16-byte aligned
+ * (idx: 4-byte); anything else, a NULL where none is allowed or an unknown dtype: FS_EINVAL, nothing launched.
+ * fs_pool2_fwd: nn.MaxPool2d(2, stride=2) of dense x [N][H][W][C] (H, W even).  Output pixel m = (n, ho, wo) goes to
+ *   y + m * y_pix + y_off (elements): a dense output is y_pix = C, y_off = 0, a channel slice of a wider buffer its pixel
+ *   stride and the slice's first channel; nothing outside the slice is touched.  idx [N][H/2][W/2][C]: one byte per output
+ *   element, the window position 2 * r + s of the maximum.  Position 0 is taken as it is, a later one where it is strictly
+ *   greater — ties go to the first position in row-major order (as ATen), and NaN as fs_maxpool_fwd treats it: it stays
+ *   the maximum where it stands at position 0 and is never picked at another one (ATen propagates it from anywhere).
+ * fs_pool2_bwd: dx [N][H][W][C] dense, every element written exactly once: dy of its window where idx names its position,
+ *   else 0, + addend (dense like dx, or NULL).  dy is addressed like fs_pool2_fwd's y (dy_pix, dy_off).  No atomics.
+ * fs_cat_fwd / fs_cat_bwd: n <= FS_CAT_MAX dense parts [M][C[i]] and the wide tensor [M][Ctot] whose channels
+ *   [off[i], off[i] + C[i]) belong to part i (slices must not overlap), all of them in ONE launch.  Forward: the slices
+ *   are written from the parts.  Backward: part i = its slice of wide, accumulate[i] != 0: part i += its slice.  A part
+ *   given as NULL is skipped — its producer wrote the slice itself, or its consumer reads the slice in place. */
+#define FS_CAT_MAX 8
+typedef struct FsCatArgs {
+  void* part[8];
+  void* wide;
+  int64_t M;
+  int32_t C[8], off[8], accumulate[8];
+  int32_t Ctot, n;
+} FsCatArgs;
+int fs_pool2_fwd(const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, int64_t y_pix, int64_t y_off,
+                 int dtype, void* stream);
+int fs_pool2_bwd(const void* dy, const uint8_t* idx, const void* addend, void* dx, int N, int H, int W, int C,
+                 int64_t dy_pix, int64_t dy_off, int dtype, void* stream);
+int fs_cat_fwd(const FsCatArgs* args, int dtype, void* stream);
+int fs_cat_bwd(const FsCatArgs* args, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1819,7 +1819,65 @@ def gen_dla_up():
         os.path.getsize(path) // 1024))
 
 
+def gen_dla():
+    """The reference's REAL dla.py classes on the CPU (tests/helpers_dla.py holds the inputs and the run helper).  Stored,
+    as float32 roundings of the f64 results where they are arrays: the state_dict keys and shapes of the ten factories;
+    per-key sum and abs-sum of a freshly initialised dla34 under one torch seed; and for DLA-34 and a small Bottleneck /
+    residual_root network one training-mode forward and backward at N = 2, 64 x 64 — the f64 features, per level the
+    (max, rms) deviation of the fp32 run and of the fp32 run whose convolutions read bf16-rounded operands, for every
+    parameter and the input the f64 gradient norm and the L2 norm of both runs' gradient deviations, the names without
+    gradient, every BatchNorm buffer after the forward and the two runs' deviations of the running statistics."""
+    import importlib
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from tests import helpers_dla as HL
+    ref = importlib.import_module("vision_base.networks.models.backbone.dla")
+    gold = {"factories": np.array(HL.FACTORIES)}
+    for name in HL.FACTORIES:
+        sd = HL.build_factory(ref, name).state_dict()
+        gold[name + "/keys"] = np.array(list(sd))
+        gold[name + "/shapes"] = np.array([",".join(map(str, v.shape)) for v in sd.values()])
+    torch.manual_seed(HL.INIT_SEED)
+    sd = HL.build_factory(ref, "dla34").state_dict()
+    gold["init/sum"] = np.array([float(v.double().sum()) for v in sd.values()])
+    gold["init/abs_sum"] = np.array([float(v.double().abs().sum()) for v in sd.values()])
+    for which in HL.NETS:
+        x, cots = HL.net_inputs(which)
+        runs = {}
+        for tag, dtype, rounded in (("f64", torch.float64, False), ("fp32", torch.float32, False), ("bf16", torch.float32, True)):
+            m = HL.build_net(ref, which)
+            m.load_state_dict(HL.net_state(m, which), strict=True)
+            if rounded:
+                HL.round_conv_operands_to_bf16(m)
+            runs[tag] = HL.run_net(m, x, cots, dtype)
+        feats, g64, none, bufs = runs["f64"]
+        names = sorted(g64)
+        gold[which + "/keys"] = np.array(list(m.state_dict()))
+        gold[which + "/none_names"] = np.array(none)
+        gold[which + "/grad_names"] = np.array(names)
+        gold[which + "/grad_norm"] = np.array([float(g64[k].norm()) for k in names])
+        for i, f in enumerate(feats):
+            gold["%s/feat%d" % (which, i)] = npy(f).astype(np.float32)
+        gold[which + "/buf_names"] = np.array(sorted(bufs))
+        for k in bufs:
+            gold["%s/buf/%s" % (which, k)] = npy(bufs[k]).astype(np.int64 if k.endswith("tracked") else np.float32)
+        for tag in ("fp32", "bf16"):
+            f2, g2, none2, b2 = runs[tag]
+            assert none2 == none and sorted(g2) == names
+            gold["%s/feat_dev_%s" % (which, tag)] = np.array([HL.deviation(a, b) for a, b in zip(f2, feats)])
+            gold["%s/grad_dev_%s" % (which, tag)] = np.array([float((g2[k].double() - g64[k]).norm()) for k in names])
+            gold["%s/buf_dev_%s" % (which, tag)] = np.array([HL.buffer_deviation(b2, bufs, sfx) for sfx in ("running_mean", "running_var")])
+        print("dla %s: %d features, %d gradients, %d without; fp32 feature deviation max %.1e, bf16-operand %.1e" % (
+            which, len(feats), len(names), len(none), gold[which + "/feat_dev_fp32"][:, 0].max(),
+            gold[which + "/feat_dev_bf16"][:, 0].max()))
+    path = os.path.join(GOLD, "dla.npz")
+    np.savez_compressed(path, **gold)
+    print("dla.npz: %d KiB" % (os.path.getsize(path) // 1024))
+
+
 if __name__ == "__main__":
+    if "--only-dla" in sys.argv:
+        gen_dla()
+        sys.exit(0)
     if "--only-dla-up" in sys.argv:
         gen_dla_up()
         sys.exit(0)
@@ -1928,6 +1986,7 @@ if __name__ == "__main__":
     gen_postopt()
     gen_motion_mask()
     gen_dla_up()
+    gen_dla()
     gen_augment_ext()
     for f in sorted(os.listdir(GOLD)):
         print(f, os.path.getsize(os.path.join(GOLD, f)) // 1024, "KiB")
