@@ -57,7 +57,7 @@ __host__ __device__ inline bool dense(long sN, long sH, long sW, int H, int W, i
 }
 
 // A replicate-padded buffer [N, H+2, W+2, C] holds interior pixel (h, w) at (h+1, w+1) and, for an edge pixel, at the
-// border copies next to it: site(hp, wp) is called for each.  (H, W >= 2: decoder maps are never a single row/column)
+// border copies next to it: site(hp, wp) is called for each.  (H, W >= 2: bn_apply_check / bn_bwd_check refuse less)
 template <typename F>
 __device__ __forceinline__ void for_pad_sites(int h, int w, int H, int W, F site) {
   int hs[2] = {h + 1, 0}, ws[2] = {w + 1, 0};
@@ -906,6 +906,9 @@ int bn_apply_check(const FsBnApplyArgs* a) {
   if (a->C % 8 != 0 || a->C > MAXC || a->M <= 0) return FS_EINVAL;
   if (a->gamma2 && (!a->res || !a->beta2 || !a->save_mean2 || !a->save_invstd2)) return FS_EINVAL;
   if (a->gamma2 && !a->stats2 && (!a->running_mean2 || !a->running_var2)) return FS_EINVAL;
+  // a replicated border has two copies per edge pixel only on a map of at least 2 x 2 (for_pad_sites): on a single row or
+  // column one border line would stay unwritten
+  if (a->pad_out && (a->H < 2 || a->W < 2)) return FS_EINVAL;
   const int G = bn_groups(*a);
   if (a->M % G != 0 || (G > 1 && !a->stats)) return FS_EINVAL;
   return FS_OK;
@@ -928,6 +931,7 @@ int bn_bwd_check(const FsBnBwdArgs* a, bool apply) {
     return FS_OK;
   }
   if (a->relu && !a->y) return FS_EINVAL;
+  if (a->fold && (a->H < 2 || a->W < 2)) return FS_EINVAL;      // (as pad_out in bn_apply_check: one border line would not fold)
   return FS_OK;
 }
 

@@ -638,7 +638,8 @@ int fs_nchw_to_nhwc(const float* a, const float* b, void* dst, int N, int Ca, in
  * statistics (momentum, unbiased variance) and num_batches_tracked and saves mean / invstd.
  * stats == NULL selects eval mode: normalise with running_mean / running_var (no updates).
  * pad_out: y is [N,H+2,W+2,C] and receives a replicated border (consumer conv pads 'replicate',
- * depth_encoder.py:59,62).
+ * depth_encoder.py:59,62).  pad_out needs H >= 2 and W >= 2 (FS_EINVAL otherwise, nothing is launched): on a single
+ * row or column an edge pixel is both edges at once and one border line would stay unwritten.
  */
 typedef struct FsBnApplyArgs {
   const void* x;        /* dense [M][C] raw conv output */
@@ -683,7 +684,8 @@ int fs_bn_finalize(const FsBnApplyArgs* args, float* scale, float* shift, void* 
  *           (sums is f64 [FS_STAT_SLOTS][2][C], zeroed by the caller)
  *   apply : dx = gamma*invstd*(g - sums0/count - xhat*sums1/count); dgamma += sums1, dbeta += sums0
  *           (from sums_local when given); optional g_out = g (gradient of the residual branch).
- * fold: dout is a replicate-padded [N,H+2,W+2,C] gradient whose border folds onto the edge pixels.
+ * fold: dout is a replicate-padded [N,H+2,W+2,C] gradient whose border folds onto the edge pixels; H >= 2 and W >= 2
+ * (FS_EINVAL otherwise, from either pass, nothing is launched).
  */
 typedef struct FsBnBwdArgs {
   const void* dout; const void* y; const void* x;
