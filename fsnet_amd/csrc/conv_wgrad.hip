@@ -923,6 +923,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_narrow_kernel(const FsWgradArgs 
 // all 64 output channels and keeps them in accumulators over the block's tiles; one fp32 slab per block at the end.
 // ---------------------------------------------------------------------------------------------
 struct StemGeom { int tiles_x, tiles_y, ntiles, tiles_per_block; FsDiv dTX, dTY; };
+constexpr long kStemSlab = 64 * 49 * 8;      // floats of one persistent block's slab: 64 output channels x 49 taps x 8 channels
 
 __global__ __launch_bounds__(256) void wgrad_stem_kernel(const FsDual<FsWgradArgs, StemGeom> d) {
   const int prob = (int)blockIdx.x >= d.nb0 ? 1 : 0;
@@ -1125,7 +1126,7 @@ int launch_wgrad_stem(const FsWgradArgs& a, const FsWgradArgs* a2, hipStream_t s
   const int tiles_x = (a.Wd + 15) / 16, tiles_y = (a.Hd + 7) / 8;
   const long ntiles = (long)(a.M / (a.Hd * a.Wd)) * tiles_x * tiles_y;
   const long ntiles2 = a2 ? (long)(a2->M / (a2->Hd * a2->Wd)) * tiles_x * tiles_y : 0;
-  const long slab = 64 * 49 * 8;
+  const long slab = kStemSlab;
   // one slab per persistent block (100 KB each, written and re-read), as many blocks as the device holds at once
   static const int slots = wg_resident_blocks(wgrad_stem_kernel, 256);   // (320 blocks of this one-block-per-CU kernel ran as two rounds)
   const long max_blocks = std::min<long>(slots, a.workspace_elems / slab);
@@ -1370,10 +1371,11 @@ int launch_wgrad(const FsWgradArgs& a, const FsWgradArgs* a2, hipStream_t st) {
   const WgPath path = wgrad_path<T>(a);
   if (a2) {
     // (the stem pairs although the two encoders' Ci differ — 3 and 6 real channels of the same 8-channel pixels: dW is
-    // written through each problem's own Ci)
+    // written through each problem's own Ci).  Every persistent stem block leaves a slab, so the shared launch needs
+    // room for two; a workspace that holds one serves the two launches one after the other.
     const bool stem_pair = path == WG_STEM && wgrad_path<T>(*a2) == WG_STEM && a.Hd == a2->Hd && a.Wd == a2->Wd && a.Hs == a2->Hs &&
-                           a.Ws == a2->Ws && a.sH == a2->sH && a.sW == a2->sW;
-    if (!(stem_pair || (path != WG_NARROW && path == wgrad_path<T>(*a2) && wgrad_pairable(a, *a2))) || !a.workspace) {
+                           a.Ws == a2->Ws && a.sH == a2->sH && a.sW == a2->sW && a.workspace_elems >= 2 * kStemSlab;
+    if (!(path == WG_STEM ? stem_pair : (path != WG_NARROW && path == wgrad_path<T>(*a2) && wgrad_pairable(a, *a2))) || !a.workspace) {
       const int r = launch_wgrad<T>(a, nullptr, st);
       return r != FS_OK ? r : launch_wgrad<T>(*a2, nullptr, st);
     }

@@ -45,6 +45,10 @@ CASES = [
     (64, 64, 1, 1, 0, 4, 40, 64),     # 64 x 64 tiles
     (128, 128, 1, 1, 0, 3, 27, 31),   # 2511 pixels: the last stage is ragged (rows past the end read as zero)
     (256, 512, 1, 2, 0, 4, 40, 64),   # strided projection with 2560 output pixels
+    # the decoder's 3x3s as it runs them (ConvLayer(valid_over_padded=True)): pad 0 over a buffer the producer padded
+    (16, 16, 3, 1, 0, 2, 50, 66),     # narrow wgrad
+    (96, 32, 3, 1, 0, 2, 26, 42),
+    (64, 64, 3, 1, 0, 2, 18, 34),
 ]
 
 
