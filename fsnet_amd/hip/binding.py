@@ -254,6 +254,38 @@ class FsCatArgs(C.Structure):
     ]
 
 
+class FsDwconv7Args(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("wtab", C.c_void_p), ("bias", C.c_void_p), ("addend", C.c_void_p), ("out", C.c_void_p),
+        ("dy", C.c_void_p), ("dw", C.c_void_p), ("dbias", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+        ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("Cp", C.c_int32),
+        ("x_f32", C.c_int32), ("out_f32", C.c_int32), ("addend_f32", C.c_int32), ("flip", C.c_int32), ("accumulate", C.c_int32),
+    ]
+
+
+class FsLayerNormArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("y", C.c_void_p),
+        ("mean", C.c_void_p), ("rstd", C.c_void_p),
+        ("dy", C.c_void_p), ("addend", C.c_void_p), ("dx", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+        ("M", C.c_int64), ("C", C.c_int32), ("Cp", C.c_int32), ("eps", C.c_float),
+        ("x_f32", C.c_int32), ("y_f32", C.c_int32), ("addend_f32", C.c_int32), ("accumulate", C.c_int32),
+    ]
+
+
+class FsScaleResidualArgs(C.Structure):
+    _fields_ = [
+        ("inp", C.c_void_p), ("z", C.c_void_p), ("gamma", C.c_void_p), ("keep", C.c_void_p),
+        ("out", C.c_void_p), ("out_c", C.c_void_p),
+        ("dout", C.c_void_p), ("dz", C.c_void_p), ("dgamma", C.c_void_p), ("dbias", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+        ("HW", C.c_int64), ("N", C.c_int32), ("C", C.c_int32), ("Cp", C.c_int32),
+        ("stream_f32", C.c_int32), ("accumulate", C.c_int32),
+    ]
+
+
 ABI_VERSION = 15    # FS_ABI_VERSION of include/fsnet_hip.h (tests/test_abi.py holds the two together)
 _lib = None
 

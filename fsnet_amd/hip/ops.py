@@ -7,7 +7,7 @@ import torch
 from torch.nn.modules.utils import _pair
 
 from .binding import (lib, check, stream_ptr, FS_CAT_MAX, FsBnApplyArgs, FsBnBwdArgs, FsCatArgs, FsDcnArgs, FsDistillUnscaledArgs, FsFlowArgs,
-                      FsMotionMaskArgs, FsPhotoArgs, FsPhotoMeiMultiArgs, FsPhotoMultiArgs, FsPostOptArgs, FsSmoothArgs)
+                      FsDwconv7Args, FsLayerNormArgs, FsScaleResidualArgs, FsMotionMaskArgs, FsPhotoArgs, FsPhotoMeiMultiArgs, FsPhotoMultiArgs, FsPostOptArgs, FsSmoothArgs)
 from .conv import dtype_code, roundup, _timed, BN_EPS, BN_MOMENTUM, Spec, run_specs
 
 STAT_SLOTS = 8   # FS_STAT_SLOTS in include/fsnet_hip.h
@@ -1600,3 +1600,226 @@ def cat_bwd(wide, parts, offs, widths, accumulate=None):
     _timed("cat_bwd", nb, lambda: check(lib.fs_cat_bwd(C.byref(a), dtype_code(wide.dtype), stream_ptr()), "cat_bwd"),
            tag=str(tuple(wide.shape)))
     return parts
+
+
+# ---------------------------------------------------------------------------------- ConvNeXt backbone (convnext.hip)
+def _rows(t):
+    """dense [..., Cp] -> (rows, Cp)"""
+    assert t.is_contiguous()
+    return t.numel() // t.shape[-1], t.shape[-1]
+
+
+def _is_f32(t, code):
+    return int(t.dtype == torch.float32 and code != dtype_code(torch.float32))
+
+
+def _check_kind(t, dtype):
+    assert t.dtype in (dtype, torch.float32), (t.dtype, dtype)
+
+
+def dwconv7_tile(dtype):
+    """(rows, columns, channels) of the outputs one fs_dwconv7_fwd block owns"""
+    r, c, ch = C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib.fs_dwconv7_tile(dtype_code(dtype), C.byref(r), C.byref(c), C.byref(ch)), "dwconv7_tile")
+    return r.value, c.value, ch.value
+
+
+def dwconv7_table(weight, bias, Cp):
+    """[C,1,7,7] (+ [C]) fp32 -> the tap-major table [49][Cp] and the padded bias [Cp] the kernels read"""
+    Cc = weight.shape[0]
+    tab = torch.zeros(49, Cp, dtype=torch.float32, device=weight.device)
+    tab[:, :Cc] = weight.detach().reshape(Cc, 49).t()
+    b = None
+    if bias is not None:
+        b = torch.zeros(Cp, dtype=torch.float32, device=weight.device)
+        b[:Cc] = bias.detach()
+    return tab, b
+
+
+def dwconv7_fwd(x, tab, bias, Cc, dtype, out_dtype=None, flip=False, addend=None, out=None):
+    """depthwise 7x7 / pad 3 of dense NHWC x [N,H,W,Cp] (compute dtype or fp32) -> out in out_dtype (compute dtype or fp32);
+    flip + addend: the data gradient (x = dy, addend = the residual path's gradient, in the compute dtype or fp32)"""
+    N, H, W, Cp = x.shape
+    code = dtype_code(dtype)
+    _check_kind(x, dtype)
+    out_dtype = out_dtype or dtype
+    if out is None:
+        out = torch.empty(N, H, W, Cp, dtype=out_dtype, device=x.device)
+    assert x.is_contiguous() and out.is_contiguous() and out.shape == x.shape and tab.shape == (49, Cp)
+    assert addend is None or (addend.is_contiguous() and addend.shape == out.shape and addend.dtype in (dtype, torch.float32))
+    a = FsDwconv7Args()
+    a.x, a.wtab, a.bias, a.addend, a.out = x.data_ptr(), tab.data_ptr(), _p(bias), _p(addend), out.data_ptr()
+    a.N, a.H, a.W, a.C, a.Cp = N, H, W, Cc, Cp
+    a.x_f32, a.out_f32, a.flip = _is_f32(x, code), _is_f32(out, code), int(bool(flip))
+    a.addend_f32 = _is_f32(addend, code) if addend is not None else 0
+    _timed("dwconv7_bwd_data" if flip else "dwconv7_fwd", 2.0 * 49 * N * H * W * Cc,
+           lambda: check(lib.fs_dwconv7_fwd(C.byref(a), code, stream_ptr()), "dwconv7_fwd"), tag=str(tuple(x.shape)))
+    return out
+
+
+def dwconv7_bwd_weight(dy, x, Cc, dw=None, dbias=None, accumulate=False, want_weight=True, want_bias=True):
+    """-> (dw fp32 [C,1,7,7], dbias fp32 [C]) in a fixed summation order; dy in the compute dtype, x in it or fp32.
+    dw / dbias given: written (accumulate: added to) in place; a None with want_* False is skipped"""
+    N, H, W, Cp = x.shape
+    dtype = dy.dtype
+    code = dtype_code(dtype)
+    _check_kind(x, dtype)
+    assert x.is_contiguous() and dy.is_contiguous() and dy.shape == x.shape
+    dev = x.device
+    if dw is None and want_weight:
+        assert not accumulate
+        dw = torch.empty(Cc, 1, 7, 7, dtype=torch.float32, device=dev)
+    if dbias is None and want_bias:
+        assert not accumulate
+        dbias = torch.empty(Cc, dtype=torch.float32, device=dev)
+    nbytes = int(lib.fs_dwconv7_workspace_bytes(N, H, W, Cp))
+    assert nbytes > 0
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    a = FsDwconv7Args()
+    a.x, a.dy, a.dw, a.dbias = x.data_ptr(), dy.data_ptr(), _p(dw), _p(dbias)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    a.N, a.H, a.W, a.C, a.Cp = N, H, W, Cc, Cp
+    a.x_f32, a.accumulate = _is_f32(x, code), int(bool(accumulate))
+    _timed("dwconv7_bwd_weight", 2.0 * 49 * N * H * W * Cc,
+           lambda: check(lib.fs_dwconv7_bwd_weight(C.byref(a), code, stream_ptr()), "dwconv7_bwd_weight"), tag=str(tuple(x.shape)))
+    return dw, dbias
+
+
+def layernorm_fwd(x, gamma, beta, eps, dtype, out_dtype=None):
+    """LayerNorm over the C = gamma.numel() real channels of dense [..., Cp] x -> (y, mean, rstd)"""
+    M, Cp = _rows(x)
+    code = dtype_code(dtype)
+    _check_kind(x, dtype)
+    y = torch.empty(x.shape, dtype=out_dtype or dtype, device=x.device)
+    mean = torch.empty(M, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
+    a = FsLayerNormArgs()
+    a.x, a.gamma, a.beta, a.y, a.mean, a.rstd = x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr()
+    a.M, a.C, a.Cp, a.eps = M, gamma.numel(), Cp, float(eps)
+    a.x_f32, a.y_f32 = _is_f32(x, code), _is_f32(y, code)
+    _timed("layernorm_fwd", x.numel() * (x.element_size() + y.element_size()),
+           lambda: check(lib.fs_layernorm_fwd(C.byref(a), code, stream_ptr()), "layernorm_fwd"), tag=str(tuple(x.shape)))
+    return y, mean, rstd
+
+
+def layernorm_bwd(dy, x, gamma, mean, rstd, dtype, addend=None, dgamma=None, dbeta=None, accumulate=False, want_dx=True):
+    """-> dx (typed like x; + addend) or None; dgamma / dbeta (fp32 [C], given): written (accumulate: added to) in slab order"""
+    M, Cp = _rows(x)
+    code = dtype_code(dtype)
+    _check_kind(x, dtype)
+    _check_kind(dy, dtype)
+    assert dy.is_contiguous() and dy.shape == x.shape
+    assert addend is None or (addend.is_contiguous() and addend.shape == x.shape)
+    dx = torch.empty_like(x) if want_dx else None
+    a = FsLayerNormArgs()
+    a.x, a.gamma, a.dy, a.addend, a.dx = x.data_ptr(), gamma.data_ptr(), dy.data_ptr(), _p(addend), _p(dx)
+    a.mean, a.rstd, a.dgamma, a.dbeta = mean.data_ptr(), rstd.data_ptr(), _p(dgamma), _p(dbeta)
+    ws = None
+    if dgamma is not None or dbeta is not None:
+        nbytes = int(lib.fs_layernorm_workspace_bytes(M, Cp))
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    a.M, a.C, a.Cp = M, gamma.numel(), Cp
+    a.x_f32, a.y_f32, a.accumulate = _is_f32(x, code), _is_f32(dy, code), int(bool(accumulate))
+    a.addend_f32 = _is_f32(addend, code) if addend is not None else 0
+    _timed("layernorm_bwd", x.numel() * (2 * x.element_size() + 2 * dy.element_size()),
+           lambda: check(lib.fs_layernorm_bwd(C.byref(a), code, stream_ptr()), "layernorm_bwd"), tag=str(tuple(x.shape)))
+    return dx
+
+
+def gelu_fwd(x):
+    """exact (erf) GELU of a dense tensor in the compute dtype"""
+    assert x.is_contiguous()
+    y = torch.empty_like(x)
+    _timed("gelu_fwd", 2 * x.numel() * x.element_size(),
+           lambda: check(lib.fs_gelu_fwd(x.data_ptr(), y.data_ptr(), x.numel(), dtype_code(x.dtype), stream_ptr()), "gelu_fwd"),
+           tag=str(tuple(x.shape)))
+    return y
+
+
+def gelu_bwd(x, dy):
+    """dy * gelu'(x), x the pre-activation"""
+    assert x.is_contiguous() and dy.is_contiguous() and dy.shape == x.shape and dy.dtype == x.dtype
+    dx = torch.empty_like(x)
+    _timed("gelu_bwd", 3 * x.numel() * x.element_size(),
+           lambda: check(lib.fs_gelu_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), dtype_code(x.dtype), stream_ptr()),
+                         "gelu_bwd"), tag=str(tuple(x.shape)))
+    return dx
+
+
+def _scale_residual_args(ref, Cc, code):
+    N, Cp = ref.shape[0], ref.shape[-1]
+    a = FsScaleResidualArgs()
+    a.N, a.HW, a.C, a.Cp = N, ref.numel() // (N * Cp), Cc, Cp
+    a.stream_f32 = _is_f32(ref, code)
+    return a
+
+
+def scale_residual_fwd(inp, z, gamma, keep, Cc, want_copy=False):
+    """out = inp + keep[n] * gamma[c] * z -> (out typed like inp, its copy in z's dtype or None); gamma / keep None: ones"""
+    code = dtype_code(z.dtype)
+    _check_kind(inp, z.dtype)
+    assert inp.is_contiguous() and z.is_contiguous() and inp.shape == z.shape
+    out = torch.empty_like(inp)
+    copy = torch.empty_like(z) if want_copy else None
+    a = _scale_residual_args(inp, Cc, code)
+    a.inp, a.z, a.gamma, a.keep, a.out, a.out_c = inp.data_ptr(), z.data_ptr(), _p(gamma), _p(keep), out.data_ptr(), _p(copy)
+    _timed("scale_residual_fwd", inp.numel() * (2 * inp.element_size() + z.element_size()),
+           lambda: check(lib.fs_scale_residual_fwd(C.byref(a), code, stream_ptr()), "scale_residual_fwd"), tag=str(tuple(z.shape)))
+    return out, copy
+
+
+def scale_residual_bwd(dout, z, gamma, keep, Cc, dtype, dgamma=None, dbias=None, accumulate=False):
+    """-> dz = keep[n] * gamma[c] * dout in the compute dtype; dgamma (fp32 [C], given): sum keep[n] * dout * z; dbias (fp32
+    [C], given): gamma[c] * sum keep[n] * dout, the gradient of the bias behind z; both in slab order"""
+    code = dtype_code(dtype)
+    _check_kind(dout, dtype)
+    assert dout.is_contiguous() and (z is None or (z.is_contiguous() and z.shape == dout.shape and z.dtype == dtype))
+    dz = torch.empty(dout.shape, dtype=dtype, device=dout.device)
+    a = _scale_residual_args(dout, Cc, code)
+    a.dout, a.z, a.gamma, a.keep, a.dz, a.dgamma = dout.data_ptr(), _p(z), _p(gamma), _p(keep), dz.data_ptr(), _p(dgamma)
+    a.dbias = _p(dbias)
+    ws = None
+    if dgamma is not None or dbias is not None:
+        nbytes = int(lib.fs_scale_residual_workspace_bytes(a.N * a.HW, a.Cp))
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dout.device)
+        a.workspace, a.workspace_bytes, a.accumulate = ws.data_ptr(), nbytes, int(bool(accumulate))
+    _timed("scale_residual_bwd", dout.numel() * (dout.element_size() + 2 * dz.element_size()),
+           lambda: check(lib.fs_scale_residual_bwd(C.byref(a), code, stream_ptr()), "scale_residual_bwd"), tag=str(tuple(dout.shape)))
+    return dz
+
+
+def bias_grad(x, dbias, accumulate=True):
+    """dbias[c] (+)= column sums of dense x [..., Cp], c < dbias.numel(), in a fixed order"""
+    M, Cp = _rows(x)
+    nbytes = int(lib.fs_scale_residual_workspace_bytes(M, Cp))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    code = dtype_code(x.dtype)
+    _timed("bias_grad", x.numel() * x.element_size(),
+           lambda: check(lib.fs_bias_grad(x.data_ptr(), dbias.data_ptr(), ws.data_ptr(), nbytes, M, dbias.numel(), Cp, 0,
+                                          int(bool(accumulate)), code, stream_ptr()), "bias_grad"), tag=str(tuple(x.shape)))
+    return dbias
+
+
+def patch_gather(x, k):
+    """dense NHWC [N,H,W,Cp] -> [N,H//k,W//k,k*k*Cp] in (r, s, c) order: the operand of a kernel-k / stride-k convolution as a
+    1x1 one"""
+    N, H, W, Cp = x.shape
+    assert x.is_contiguous()
+    out = torch.empty(N, H // k, W // k, k * k * Cp, dtype=x.dtype, device=x.device)
+    _timed("patch_gather", 2 * out.numel() * x.element_size(),
+           lambda: check(lib.fs_patch_gather(x.data_ptr(), out.data_ptr(), N, H, W, Cp, k, dtype_code(x.dtype), stream_ptr()),
+                         "patch_gather"), tag=str(tuple(x.shape)))
+    return out
+
+
+def patch_scatter(dg, H, W, k):
+    """the inverse: [N,H//k,W//k,k*k*Cp] -> [N,H,W,Cp], zero in the rows and columns the floor drops"""
+    N, Ho, Wo, K = dg.shape
+    Cp = K // (k * k)
+    assert dg.is_contiguous() and Ho == H // k and Wo == W // k and Cp * k * k == K
+    dx = torch.empty(N, H, W, Cp, dtype=dg.dtype, device=dg.device)
+    _timed("patch_scatter", 2 * dx.numel() * dg.element_size(),
+           lambda: check(lib.fs_patch_scatter(dg.data_ptr(), dx.data_ptr(), N, H, W, Cp, k, dtype_code(dg.dtype), stream_ptr()),
+                         "patch_scatter"), tag=str(tuple(dx.shape)))
+    return dx

@@ -148,6 +148,22 @@ SIGNATURES = {
     "fs_pool2_bwd": (C.c_int, [P, P, P, P, I, I, I, I, L, L, I, P]),
     "fs_cat_fwd": (C.c_int, [P, I, P]),
     "fs_cat_bwd": (C.c_int, [P, I, P]),
+    # added under ABI 15: the ConvNeXt backbone's launches (FsDwconv7Args, FsLayerNormArgs, FsScaleResidualArgs; convnext.py)
+    "fs_dwconv7_fwd": (C.c_int, [P, I, P]),
+    "fs_dwconv7_bwd_weight": (C.c_int, [P, I, P]),
+    "fs_dwconv7_workspace_bytes": (C.c_int64, [I, I, I, I]),
+    "fs_dwconv7_tile": (C.c_int, [I, P, P, P]),
+    "fs_layernorm_fwd": (C.c_int, [P, I, P]),
+    "fs_layernorm_bwd": (C.c_int, [P, I, P]),
+    "fs_layernorm_workspace_bytes": (C.c_int64, [L, I]),
+    "fs_gelu_fwd": (C.c_int, [P, P, L, I, P]),
+    "fs_gelu_bwd": (C.c_int, [P, P, P, L, I, P]),
+    "fs_scale_residual_fwd": (C.c_int, [P, I, P]),
+    "fs_scale_residual_bwd": (C.c_int, [P, I, P]),
+    "fs_scale_residual_workspace_bytes": (C.c_int64, [L, I]),
+    "fs_bias_grad": (C.c_int, [P, P, P, L, L, I, I, I, I, I, P]),
+    "fs_patch_gather": (C.c_int, [P, P, I, I, I, I, I, I, P]),
+    "fs_patch_scatter": (C.c_int, [P, P, I, I, I, I, I, I, P]),
 }
 
 

@@ -1,6 +1,10 @@
 """ConvBnReLU parameter container (reference vision_base/networks/blocks/blocks.py:33-54): keys
 `sequence.0.{weight,bias}` (conv) and `sequence.1.*` (BatchNorm2d).  The arithmetic runs in the
-HIP engine (fsnet_amd/engine/nets.py); standalone forward is a single fused conv+BN+ReLU unit."""
+HIP engine (fsnet_amd/engine/nets.py); standalone forward is a single fused conv+BN+ReLU unit.
+
+DropPath (reference blocks.py:418-440): stochastic depth per sample.  The ConvNeXt runner draws the same numbers with the
+same expression and hands the factor to fs_scale_residual_fwd (fsnet_amd/engine/convnext_net.py)."""
+import torch
 import torch.nn as nn
 
 
@@ -23,3 +27,22 @@ class ConvBnReLU(nn.Module):
         raise NotImplementedError(
             "ConvBnReLU is executed by its owning network's HIP runner (DepthDecoder); standalone use is not on "
             "the monodepth hot path")
+
+
+class DropPath(nn.Module):
+    """per-sample stochastic depth on a residual branch: a sample is kept with probability 1 - drop_prob and a kept one is
+    scaled by 1 / (1 - drop_prob); the identity at rate 0 and in eval mode"""
+
+    def __init__(self, drop_prob=0.):
+        super().__init__()
+        self.drop_prob = drop_prob
+        self.keep_prob = 1 - drop_prob
+
+    def keep_mask(self, n, dtype, device, ndim):
+        """0 / 1 per sample, [n, 1, ..., 1]: floor(keep_prob + U[0, 1)) — one torch.rand draw of n numbers"""
+        return (self.keep_prob + torch.rand((n,) + (1,) * (ndim - 1), dtype=dtype, device=device)).floor_()
+
+    def forward(self, x):
+        if self.drop_prob == 0. or not self.training:
+            return x
+        return x.div(self.keep_prob) * self.keep_mask(x.shape[0], x.dtype, x.device, x.ndim)

@@ -1105,6 +1105,101 @@ int fs_pool2_bwd(const void* dy, const uint8_t* idx, const void* addend, void* d
 int fs_cat_fwd(const FsCatArgs* args, int dtype, void* stream);
 int fs_cat_bwd(const FsCatArgs* args, int dtype, void* stream);
 
+/* Added under ABI 15: what the ConvNeXt backbone (vision_base/networks/models/backbone/convnext.py) needs beside the
+ * convolution launches.  Activations are dense NHWC with a pixel stride of Cp >= C channels, Cp a whole number of 16-byte
+ * units of the compute dtype (8 bf16 / 4 fp32); C is the real channel count.  A tensor with a *_f32 flag set is fp32
+ * whatever the compute dtype (the residual stream); with fp32 compute the flags mean nothing.  Every sum is fp32, every
+ * output's channels [C, Cp) are written as zeros, every pointer is 16-byte aligned (the fp32 parameter vectors need not
+ * be).  No float atomics: a parameter gradient is summed per slab of rows (the slabs a fixed function of the shape) into
+ * `workspace` (>= fs_*_workspace_bytes) and added up in slab order by a second launch, `accumulate` != 0: onto what the
+ * destination holds.  A NULL where none is allowed, a bad size or an unknown dtype: FS_EINVAL, nothing launched.
+ *
+ * fs_dwconv7_fwd: out = bias + depthwise 7x7 (stride 1, zero padding 3) of x (+ addend, typed by addend_f32).  wtab is the
+ *   tap-major fp32 table [49][Cp] (tap r * 7 + s), bias fp32 [Cp] or NULL.  flip != 0 mirrors the taps: with x = dy, no bias
+ *   and addend = the residual path's gradient this is the data gradient.  x is staged in the compute dtype.
+ *   fs_dwconv7_tile: output rows, columns and channels of one block.
+ * fs_dwconv7_bwd_weight: dw [C][7][7] = sum dy[n,h,w,c] x[n,h+r-3,w+s-3,c] and dbias [C] = sum dy (either may be NULL);
+ *   dy is in the compute dtype.
+ * fs_layernorm_fwd: y = (x - mean) * rstd * gamma + beta over the C channels of each of M rows; mean first, then the
+ *   centred second moment; rstd = 1 / sqrt(var + eps).  mean / rstd: fp32 [M], saved.  x_f32 types x and dx, y_f32 y and dy.
+ * fs_layernorm_bwd: dx (+ addend, typed by addend_f32) where dx is given, dgamma / dbeta (fp32 [C]) where they are.
+ * fs_gelu_fwd / _bwd: exact (erf) GELU of n values in the compute dtype; the backward reads the pre-activation x.
+ * fs_scale_residual_fwd: out = inp + keep[n] * gamma[c] * z over N samples of HW rows; keep (fp32 [N]) NULL = 1, gamma
+ *   (fp32 [C]) NULL = 1; a sample with keep == 0 copies inp bit for bit.  inp / out / dout are typed by stream_f32, z / dz
+ *   are in the compute dtype; out_c (or NULL) receives out in the compute dtype as well.
+ * fs_scale_residual_bwd: dz = keep[n] * gamma[c] * dout, dgamma [C] = sum keep[n] * dout * z (where dgamma is given), and
+ *   dbias [C] = gamma[c] * sum keep[n] * dout (where given): the gradient of a bias added to z, summed before dz is rounded.
+ * fs_bias_grad: dbias [C] = column sums of dense x [M][Cp] (the gradient of a GEMM layer's bias) through a workspace of
+ *   fs_scale_residual_workspace_bytes(M, Cp), in a fixed order — fs_channel_sum joins its blocks with float atomics.
+ * fs_patch_gather: x [N][H][W][Cp] -> out [N][H/k][W/k][k*k*Cp] in (r, s, c) order (floor division; 1 <= k <= 8).
+ * fs_patch_scatter: its inverse, dg -> dx [N][H][W][Cp]; every element of dx written once, zero where the floor drops. */
+typedef struct FsDwconv7Args {
+  const void* x;
+  const float* wtab;
+  const float* bias;
+  const void* addend;
+  void* out;
+  const void* dy;
+  float* dw;
+  float* dbias;
+  float* workspace;
+  int64_t workspace_bytes;
+  int32_t N, H, W, C, Cp;
+  int32_t x_f32, out_f32, addend_f32, flip, accumulate;
+} FsDwconv7Args;
+int fs_dwconv7_fwd(const FsDwconv7Args* args, int dtype, void* stream);
+int fs_dwconv7_bwd_weight(const FsDwconv7Args* args, int dtype, void* stream);
+int64_t fs_dwconv7_workspace_bytes(int N, int H, int W, int Cp);
+int fs_dwconv7_tile(int dtype, int32_t* rows, int32_t* cols, int32_t* channels);
+typedef struct FsLayerNormArgs {
+  const void* x;
+  const float* gamma;
+  const float* beta;
+  void* y;
+  float* mean;
+  float* rstd;
+  const void* dy;
+  const void* addend;
+  void* dx;
+  float* dgamma;
+  float* dbeta;
+  float* workspace;
+  int64_t workspace_bytes;
+  int64_t M;
+  int32_t C, Cp;
+  float eps;
+  int32_t x_f32, y_f32, addend_f32, accumulate;
+} FsLayerNormArgs;
+int fs_layernorm_fwd(const FsLayerNormArgs* args, int dtype, void* stream);
+int fs_layernorm_bwd(const FsLayerNormArgs* args, int dtype, void* stream);
+int64_t fs_layernorm_workspace_bytes(int64_t M, int Cp);
+int fs_gelu_fwd(const void* x, void* y, int64_t n, int dtype, void* stream);
+int fs_gelu_bwd(const void* x, const void* dy, void* dx, int64_t n, int dtype, void* stream);
+typedef struct FsScaleResidualArgs {
+  const void* inp;
+  const void* z;
+  const float* gamma;
+  const float* keep;
+  void* out;
+  void* out_c;
+  const void* dout;
+  void* dz;
+  float* dgamma;
+  float* dbias;
+  float* workspace;
+  int64_t workspace_bytes;
+  int64_t HW;
+  int32_t N, C, Cp;
+  int32_t stream_f32, accumulate;
+} FsScaleResidualArgs;
+int fs_scale_residual_fwd(const FsScaleResidualArgs* args, int dtype, void* stream);
+int fs_scale_residual_bwd(const FsScaleResidualArgs* args, int dtype, void* stream);
+int64_t fs_scale_residual_workspace_bytes(int64_t M, int Cp);
+int fs_bias_grad(const void* x, float* dbias, float* workspace, int64_t workspace_bytes, int64_t M, int C, int Cp, int x_f32,
+                 int accumulate, int dtype, void* stream);
+int fs_patch_gather(const void* x, void* out, int N, int H, int W, int Cp, int k, int dtype, void* stream);
+int fs_patch_scatter(const void* dg, void* dx, int N, int H, int W, int Cp, int k, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
